@@ -12,7 +12,7 @@ By default every kernel is launched from Python each step, as DPVO runs; the
 host stays ahead of the GPU (--graph: capture the step once as a hipGraph and
 replay it; each replay leaves a ~8.7 us launch gap).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -20,6 +20,15 @@ Without a launcher (WORLD_SIZE unset) and N > 1, bench.py starts the N ranks
 itself (one child process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*
 in each child's environment, before anything touches the GPU) and exits with
 the worst child exit code; rank 0 prints the line.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+Every timed run starts from the same state (after the time-based warm-up the
+seeded poses, patches and pyramid ring are put back and a fixed 16 steps run),
+so with the same arguments the timed steps see the same inputs from run to
+run; --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy.  --full adds what takes runs of its own: the A-CORR roofline,
+the per-step GPU / host split and the CPU baseline (--sharded: the
+per-iteration phase split).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -151,6 +160,19 @@ def warm_until(step_fn, torch, min_ms=200.0, max_steps=100000):
     return n
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array (float32 / float64 kept, anything
+    else stored as float32)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy())
+
+
 def sharded_main(args, torch, dist, world, rank, local, dev):
     """--sharded: BASELINE cfg4 global BA (1024 frames x 96 patches, ~131k
     edges, N = 1023 free poses), edge-sharded by source frame over the ranks
@@ -189,11 +211,13 @@ def sharded_main(args, torch, dist, world, rank, local, dev):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - tt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"poses": poses})
     # phase split of one iteration on this rank: build | all_reduce | solve+update
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     poses, patches = poses0.clone(), patches0.clone()
     st = sb.state
-    reps = max(3, min(args.steps, 10))
+    reps = max(3, min(args.steps, 10)) if args.full else 0
     acc = [0.0, 0.0, 0.0]
     for _ in range(reps):
         ev[0].record()
@@ -230,10 +254,10 @@ def sharded_main(args, torch, dist, world, rank, local, dev):
                                    f"{G.F} frames x {G.M} patches, {G.E} edges, N={t1 - t0}, "
                                    f"BA {args.ba_iters} iters per call (setup included)",
                        "edges": G.E, "frames": G.F, "parallelism": f"edge-sharded x{world}"},
-            "per_iteration_ms": {"build": acc[0], "all_reduce": acc[1], "solve_update": acc[2],
-                                 "total": it_ms},
+            "per_iteration_ms": ({"build": acc[0], "all_reduce": acc[1], "solve_update": acc[2],
+                                  "total": it_ms} if args.full else None),
             "all_reduce_bytes": sb.allreduce_bytes,
-            "all_reduce_share": acc[1] / it_ms if it_ms > 0 else 0.0,
+            "all_reduce_share": (acc[1] / it_ms if it_ms > 0 else 0.0) if args.full else None,
             "ba_status": status,
             "structure": dict(zip(["status", "patches", "items", "blocks", "interior", "border",
                                    "g", "superblocks"], info)),
@@ -252,7 +276,16 @@ def main():
     ap.add_argument("--levels", default="1,2,4,8")
     ap.add_argument("--ba-iters", type=int, default=2)
     ap.add_argument("--mem", type=int, default=36, help="feature ring-buffer frames (DPVO mem)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their "
+                         "own outside the timed steps: the A-CORR roofline, the per-step GPU / "
+                         "host split and the CPU baseline (--sharded: the phase split of a BA "
+                         "iteration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (coords, corr, "
+                         "and the poses / patches it updated in place) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--overlap", action="store_true",
@@ -375,25 +408,27 @@ def main():
             cur.wait_stream(plan_stream)
         fastba.BA(poses, patches, D.intrinsics, D.target, D.weight, lmbda, D.ii, D.jj, D.kk, 1,
                   G.F, M=G.M, iterations=args.ba_iters, plan=ws)
-        return corr
+        return coords, corr
 
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
     warm_until(step, torch, args.warm_ms)
-    # A-CORR kernel time for the roofline: HIP events around the corr launch
-    # (same stream) over eager steps outside the timed region
-    n_ev = 20
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(n_ev)]
-    for i in range(n_ev):
-        step(i, evs[i])
-    torch.cuda.synchronize()
-    corr_ms = sorted(a.elapsed_time(b) for a, b in evs)[n_ev // 2]
-    coords0 = fastba.reproject(poses, patches, D.intrinsics, D.ii, D.jj, D.kk)
-    alg_bytes, per_level = algorithmic_corr_bytes(
-        coords0, [f.shape[3] for f in pyr], [f.shape[4] for f in pyr], scales, C, P, 3,
-        feat_bytes)
+    corr_ms = alg_bytes = per_level = None
+    if args.full:
+        # A-CORR kernel time for the roofline: HIP events around the corr launch
+        # (same stream) over eager steps outside the timed region
+        n_ev = 20
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(n_ev)]
+        for i in range(n_ev):
+            step(i, evs[i])
+        torch.cuda.synchronize()
+        corr_ms = sorted(a.elapsed_time(b) for a, b in evs)[n_ev // 2]
+        coords0 = fastba.reproject(poses, patches, D.intrinsics, D.ii, D.jj, D.kk)
+        alg_bytes, per_level = algorithmic_corr_bytes(
+            coords0, [f.shape[3] for f in pyr], [f.shape[4] for f in pyr], scales, C, P, 3,
+            feat_bytes)
 
     graph = None
     if args.graph:
@@ -409,7 +444,7 @@ def main():
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            step(0)
+            last = step(0)
         graph.replay()
         torch.cuda.synchronize()
 
@@ -426,45 +461,68 @@ def main():
     def run_one(i):
         if graph is not None:
             graph.replay()
-        else:
-            step(i)
+            return last
+        return step(i)
+
+    # every timed run starts from the same state, however many untimed steps
+    # the time-based warm-ups took: the seeded poses / patches and a ring in
+    # which every slot holds its inserted frame, then a fixed number of steps
+    # (so that step() calls, not the reset's copies, come right before the
+    # timed loop: see the note on the first timed step above)
+    poses.copy_(D.poses)
+    patches.copy_(D.patches)
+    for slot in range(args.mem):
+        altcorr.insert_frame(pyr_nchw[0][0, slot], pyr, slot, levels)
+    for i in range(16):
+        run_one(i)
 
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     host_s = [0.0] * args.steps
+    i_last = args.steps - 1 if args.dump_outputs else -1
     t0 = time.perf_counter()
     for i in range(args.steps):
         h = time.perf_counter()
-        run_one(i)
-        host_s[i] = time.perf_counter() - h  # host enqueue time of the step (no sync)
+        if i == i_last:
+            out_last = run_one(i)
+        else:
+            run_one(i)  # its outputs are freed at once: the next step reuses their memory
+        host_s[i] =time.perf_counter() - h  # host enqueue time of the step (no sync)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump = None
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # poses / patches are updated in place: keep the last timed step's
+        dump = {"coords": out_last[0].clone(), "corr": out_last[1].clone(),
+                "poses": poses.clone(), "patches": patches.clone()}
 
-    # per-step split, in a second pass of the same length
-    # right after the timed one (events are not recorded inside the timed loop):
-    # HIP events before / after each step on the launch stream = the GPU time
-    # of the step's kernels incl. the gaps between them; host enqueue = the
-    # wall time of the Python call (perf_counter, no sync) in the timed loop
-    n_pp = max(args.steps, 20)
-    pev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(n_pp)]
-    for i in range(n_pp):
-        pev[i][0].record()
-        run_one(i)
-        pev[i][1].record()
-    torch.cuda.synchronize()
-    gpu_ms = sorted(a.elapsed_time(b) for a, b in pev)
-    host_ms = sorted(1e3 * h for h in host_s)
-    step_split = {
-        "gpu_ms_median": gpu_ms[n_pp // 2], "gpu_ms_min": gpu_ms[0], "gpu_ms_max": gpu_ms[-1],
-        "host_enqueue_ms_median": host_ms[len(host_ms) // 2], "host_enqueue_ms_max": host_ms[-1],
-        "host_enqueue_ms_first": 1e3 * host_s[0],
-        "note": "gpu = HIP events around each step (second pass, same length); host = "
-                "perf_counter around each timed step() call without a sync",
-    }
+    step_split = None
+    if args.full:
+        # per-step split, in a second pass of the same length
+        # right after the timed one (events are not recorded inside the timed loop):
+        # HIP events before / after each step on the launch stream = the GPU time
+        # of the step's kernels incl. the gaps between them; host enqueue = the
+        # wall time of the Python call (perf_counter, no sync) in the timed loop
+        n_pp = max(args.steps, 20)
+        pev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(n_pp)]
+        for i in range(n_pp):
+            pev[i][0].record()
+            run_one(i)
+            pev[i][1].record()
+        torch.cuda.synchronize()
+        gpu_ms = sorted(a.elapsed_time(b) for a, b in pev)
+        host_ms = sorted(1e3 * h for h in host_s)
+        step_split = {
+            "gpu_ms_median": gpu_ms[n_pp // 2], "gpu_ms_min": gpu_ms[0], "gpu_ms_max": gpu_ms[-1],
+            "host_enqueue_ms_median": host_ms[len(host_ms) // 2], "host_enqueue_ms_max": host_ms[-1],
+            "host_enqueue_ms_first": 1e3 * host_s[0],
+            "note": "gpu = HIP events around each step (second pass, same length); host = "
+                    "perf_counter around each timed step() call without a sync",
+        }
 
     # every BA call of the run (warmup, event steps, graph replays) finished
     # without a fatal status (raises RuntimeError otherwise)
@@ -476,15 +534,16 @@ def main():
         allt = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allt, mine)
         per_rank = [args.steps / t.item() for t in allt]
-        t = torch.tensor([elapsed, corr_ms], device=dev, dtype=torch.float64)
+        t = torch.tensor([elapsed, corr_ms or 0.0], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, corr_ms = t[0].item(), t[1].item()
+        elapsed, corr_ms = t[0].item(), (t[1].item() if args.full else None)
 
     value = world * args.steps / elapsed
-    achieved = alg_bytes / (corr_ms * 1e-3) / 1e9  # GB/s of the dominant kernel
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import cpu_baseline  # baseline infrastructure (CPU port of the reference path)
 
@@ -510,8 +569,38 @@ def main():
                               "0.96-1.01 (profiles/r02_cpu_calibration.json); ba.py port pinned "
                               "to the reference's fp64 run (tests/test_cpu_baseline.py)"}
 
-    if rank == 0:
+    roofline = None
+    if args.full and rank == 0:
         traffic = pmc_traffic(args.config) if args.features == "f32" else None
+        achieved = alg_bytes / (corr_ms * 1e-3) / 1e9  # GB/s of the dominant kernel
+        roofline = {
+            "kernel": "corr_nhwc_lvl_kernel (A-CORR, all levels, one launch, one wave per "
+                      "(edge, level))",
+            # how the products are formed (exact fp32 for fp32 features)
+            "products": ("fp32 x fp32 on v_mfma_f32_16x16x4_f32 (IEEE fp32 products), fp32 "
+                         "accumulation"
+                         if args.features == "f32" else
+                         "fp16 x fp16 on v_mfma_f32_16x16x32_f16, fp32 accumulation"),
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            # counter (real DRAM) rate of the same launch: PMC bytes / the
+            # live kernel time; below `achieved` because edges sharing a
+            # target frame re-read overlapping boxes from L2 / MALL
+            "traffic_gbs": (traffic / (corr_ms * 1e-3) / 1e9) if traffic else None,
+            # the same as a fraction of the peak: `frac` counts every byte the
+            # kernel's loads request (the survey's per-edge count), re-reads
+            # served by L2 / MALL included, so it can exceed 1
+            "traffic_frac": (traffic / (corr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "kernel_ms": corr_ms,
+            "per_level": per_level,
+        }
+
+    if rank == 0:
         out = {
             "metric": METRIC,
             "value": value,
@@ -544,32 +633,7 @@ def main():
                 "radius": 3, "channels": C, "feature_ring": args.mem,
                 "parallelism": f"replicas x{world}",
             },
-            "roofline": {
-                "kernel": "corr_nhwc_lvl_kernel (A-CORR, all levels, one launch, one wave per "
-                          "(edge, level))",
-                # how the products are formed (exact fp32 for fp32 features)
-                "products": ("fp32 x fp32 on v_mfma_f32_16x16x4_f32 (IEEE fp32 products), fp32 "
-                             "accumulation"
-                             if args.features == "f32" else
-                             "fp16 x fp16 on v_mfma_f32_16x16x32_f16, fp32 accumulation"),
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                # counter (real DRAM) rate of the same launch: PMC bytes / the
-                # live kernel time; below `achieved` because edges sharing a
-                # target frame re-read overlapping boxes from L2 / MALL
-                "traffic_gbs": (traffic / (corr_ms * 1e-3) / 1e9) if traffic else None,
-                # the same as a fraction of the peak: `frac` counts every byte the
-                # kernel's loads request (the survey's per-edge count), re-reads
-                # served by L2 / MALL included, so it can exceed 1
-                "traffic_frac": (traffic / (corr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "kernel_ms": corr_ms,
-                "per_level": per_level,
-            },
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "ba_status": ba_status,
         }

@@ -10,7 +10,7 @@
 #   smoke      __graft_entry__.smoke()
 #   driver     bench.py exactly as the driver runs it (--steps 20 --warmup 5)
 #   long       bench.py --steps 300 --warmup 10 (no CPU baseline)
-#   bench      bench.py $BENCH_ARGS (full default run, CPU baseline included)
+#   bench      bench.py --full $BENCH_ARGS (roofline, step split and CPU baseline included)
 #   prof       rocprofv3 --kernel-trace --stats over a 200-step bench (kernel table printed)
 #   profdrv    the same over the driver's 20-step command
 #   proff16    the same over a 200-step bench with fp16 features
@@ -27,7 +27,7 @@
 #   dpvoprof   rocprofv3 over the fork's live BA call at E = 9850 (scripts/dpvo_window_call.py)
 #   corrpmc    SQ / TCC counter passes over scripts/corr_variants.py (scripts/pmc_corrvar.sh)
 #   corrwide   the channels-last corr tests incl. the wide-dynamic-range ones
-#   cfg4       bench.py --sharded (cfg4 global BA, one rank)
+#   cfg4       bench.py --sharded --full (cfg4 global BA, one rank, with the phase split)
 #   cfg4prof   rocprofv3 over the cfg4 bench
 #   pmcsq      BA/corr SQ + LDS counter passes (scripts/pmc.sh with PMC_GROUPS)
 #   traffic    corr FETCH_SIZE / WRITE_SIZE passes
@@ -63,7 +63,7 @@ for s in "$@"; do
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     driver) run driver 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 ;;
     long) run long 300 python -u bench.py --steps 300 --warmup 10 --no-cpu-baseline ;;
-    bench) run bench 400 python -u bench.py ${BENCH_ARGS:-} ;;
+    bench) run bench 400 python -u bench.py --full ${BENCH_ARGS:-} ;;
     prof) prof prof --steps 200 --warmup 10 ;;
     profdrv) prof profdrv --steps 20 --warmup 5 ;;
     proff16) prof proff16 --steps 200 --warmup 10 --features f16 ;;
@@ -93,7 +93,7 @@ for s in "$@"; do
       python scripts/kstats.py "$(find $O/${T}_dpvoprof -name '*kernel_stats.csv' | head -1)" 8 \
         | tee $O/${T}_dpvoprof_kstats.txt ;;
     corrwide) run corrwide 300 $PYT tests/test_corr_gpu.py -k "wide_range or channels_last" ;;
-    cfg4) run cfg4 300 python -u bench.py --sharded --steps 5 --warmup 2 ;;
+    cfg4) run cfg4 300 python -u bench.py --sharded --full --steps 5 --warmup 2 ;;
     cfg4prof) prof cfg4prof --sharded --steps 3 --warmup 1 ;;
     pmcsq) run pmcsq 600 env SQ_EXTRA="${SQ_EXTRA:-SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE}" bash scripts/pmc_sq.sh ;;
     traffic) run traffic 400 env PMC_GROUPS="FETCH_SIZE WRITE_SIZE" bash scripts/pmc.sh ;;
