@@ -383,10 +383,18 @@ __device__ __forceinline__ void sweeps(const float* A, const float* Z, int N, in
 }
 
 // block column k-1's LDL^T tasks go to wave 3 during factor step k when the
-// step's trailing update (n5 row pairs) leaves it idle
+// step's trailing update (n5 = 3 m (m + 1) / 2 row pairs, m = N - k - 2) leaves
+// it idle: n5 <= 128, i.e. m <= kLdlEarlyM.  The columns left over for after
+// the factorisation are therefore 0 .. ldl_left(N) - 1.
+constexpr int kLdlEarlyM = 8;
+static_assert(3 * (kLdlEarlyM * (kLdlEarlyM + 1) / 2) <= 128 &&
+                  3 * ((kLdlEarlyM + 1) * (kLdlEarlyM + 2) / 2) > 128,
+              "wave 3 is idle in the trailing update up to kLdlEarlyM");
 __device__ __forceinline__ bool ldl_early(int N, int k) {
-  const int m = N - k - 2, n5 = m > 0 ? 3 * (m * (m + 1) / 2) : 0;
-  return k >= 1 && n5 <= 128;
+  return k >= 1 && N - k - 2 <= kLdlEarlyM;
+}
+__device__ __forceinline__ int ldl_left(int N) {  // columns kc with !ldl_early(N, kc + 1)
+  return N - kLdlEarlyM - 3 > 0 ? N - kLdlEarlyM - 3 : 0;
 }
 
 // Whole workgroup (blockDim.x == 256, 1 <= N <= 16).  Solves S x = y into s.x
@@ -513,20 +521,17 @@ __device__ inline bool wsolve(const WSolve& s, int N, int refine, int* fail,
     __syncthreads();
     wstamp(st, 2 + k);
   }
-  {  // the block columns ldl_early left over (D_{N-1}^-1 is done in step N-1)
-    int tot = 0;
-    for (int kc = 0; kc + 1 < N; kc++)
-      if (!ldl_early(N, kc + 1)) tot += 6 * (N - kc);
+  // the block columns ldl_early left over (D_{N-1}^-1 is done in step N-1):
+  // none up to N = 11 (DPVO's windows), where this costs one compare (a loop
+  // over ldl_early per column was ~1.1k cycles of scalar code for no task)
+  if (const int nleft = ldl_left(N)) {
+    const int tot = 6 * (nleft * N - nleft * (nleft - 1) / 2);
     for (int t = tid; t < tot; t += blockDim.x) {
       int r = t, kc = 0;
-      for (; kc + 1 < N; kc++) {
-        if (ldl_early(N, kc + 1)) continue;
-        if (r < 6 * (N - kc)) break;
-        r -= 6 * (N - kc);
-      }
+      for (; r >= 6 * (N - kc); kc++) r -= 6 * (N - kc);
       ldl_task(s, kc, r);
     }
-    if (tot) __syncthreads();
+    __syncthreads();
   }
   wstamp(st, 40);
   const bool ok = *fail == 0;

@@ -5,12 +5,14 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I dpvo_amd/csrc \
 //         scripts/micro/wsolve_bench.hip -o scripts/micro/wsolve_bench
 //   ./scripts/micro/wsolve_bench [N=11] [refine=1] [cond_scale=300]
+//   ./scripts/micro/wsolve_bench all [refine=1] [cond_scale=300]   N = 1, 2, 10, 11, 16
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "ba_solve.hpp"
@@ -39,6 +41,7 @@ __global__ void __launch_bounds__(256) k_wsolve(const double* S, const double* y
   __shared__ long long stl[64];
   for (int k = threadIdx.x; k < 36 * NB; k += blockDim.x) Sd[k] = S[k];
   for (int k = threadIdx.x; k < n; k += blockDim.x) yd[k] = y[k];
+  for (int k = threadIdx.x; k < 64; k += blockDim.x) stl[k] = 0;  // stamps a small N never writes
   __syncthreads();
 #ifdef WSOLVE_MMA
   // the sweep solver's workspace after S, y, x (16-B aligned)
@@ -74,10 +77,7 @@ __global__ void __launch_bounds__(256) k_wsolve(const double* S, const double* y
 
 static int lb(int a, int b) { return a * (a + 1) / 2 + b; }
 
-int main(int argc, char** argv) {
-  const int N = argc > 1 ? atoi(argv[1]) : 11;
-  const int refine = argc > 2 ? atoi(argv[2]) : 1;
-  const double scale = argc > 3 ? atof(argv[3]) : 300.0;
+static int run_one(int N, int refine, double scale) {
   const int n = 6 * N, NB = N * (N + 1) / 2;
   srand(1);
   std::vector<double> G(n * 2 * n), D(n * n, 0.0), y(n);
@@ -125,6 +125,7 @@ int main(int argc, char** argv) {
   long long* dc;
   long long* dst;
   hipMalloc(&dst, sizeof(long long) * 64);
+  hipMemset(dst, 0, sizeof(long long) * 64);
   int* dfail;
   hipMalloc(&dS, sizeof(double) * Sb.size());
   hipMalloc(&dy, sizeof(double) * n);
@@ -162,8 +163,9 @@ int main(int argc, char** argv) {
   printf("pre %lld piv0 %lld |", h[1] - h[0], 0LL);
   for (int k = 0; k < N; k++) printf(" %lld", h[2 + k] - (k ? h[1 + k] : h[1]));
   printf(" | post %lld | solve %lld", h[40] - h[1 + N], h[41] - h[40]);
-  printf(" | k2 (from step start): w0 %lld w1 %lld w2 %lld w3 %lld w3+ldl %lld", h[50] - h[3],
-         h[52] - h[3], h[53] - h[3], h[54] - h[3], h[55] - h[3]);
+  if (N >= 3)  // the stamps of block step 2 exist from N = 3
+    printf(" | k2 (from step start): w0 %lld w1 %lld w2 %lld w3 %lld w3+ldl %lld", h[50] - h[3],
+           h[52] - h[3], h[53] - h[3], h[54] - h[3], h[55] - h[3]);
 #ifdef WSOLVE_STEP_STAMPS
   printf(" | w0: update %lld readlane %lld chol %lld stores %lld panel %lld", h[56] - h[3],
          h[57] - h[56], h[58] - h[57], h[59] - h[58], h[50] - h[59]);
@@ -183,5 +185,28 @@ int main(int argc, char** argv) {
   printf("N=%d refine=%d cond~%.1e fail=%d rel.err=%.3e median=%lld cyc (%.2f us @2.4GHz)\n", N,
          refine, (dmax * dmax) / (dmin * dmin), fail, sqrt(e / nr), cs[cs.size() / 2],
          cs[cs.size() / 2] / 2400.0);
+  hipFree(dst);
+  hipFree(dS);
+  hipFree(dy);
+  hipFree(dX);
+  hipFree(dc);
+  hipFree(dfail);
+  // the check: x against the host fp64 Cholesky.  One fp64 refinement step
+  // leaves ~kappa eps32^2 (1e-12 here); without refinement fp32 accuracy.
+  const double rel = sqrt(e / nr), bound = refine > 0 ? 1e-10 : 1e-4;
+  if (fail || !(rel <= bound)) {
+    printf("FAILED: N=%d fail=%d rel.err=%.3e (bound %.0e)\n", N, fail, rel, bound);
+    return 1;
+  }
   return 0;
+}
+
+int main(int argc, char** argv) {
+  const bool all = argc > 1 && std::string(argv[1]) == "all";
+  const int refine = argc > 2 ? atoi(argv[2]) : 1;
+  const double scale = argc > 3 ? atof(argv[3]) : 300.0;
+  if (!all) return run_one(argc > 1 ? atoi(argv[1]) : 11, refine, scale);
+  int rc = 0;
+  for (int N : {1, 2, 10, 11, 16}) rc |= run_one(N, refine, scale);
+  return rc;
 }
