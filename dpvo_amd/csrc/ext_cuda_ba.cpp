@@ -636,6 +636,55 @@ std::vector<torch::Tensor> ba_solve_system(torch::Tensor J_Ginv_i, torch::Tensor
   return {delta.to(torch::kFloat32).to(out_dev)};
 }
 
+// Residual (and Jacobians) of every pose-graph edge in one launch: the device
+// form of optim_utils.py:152-189 (_residual + batch_jacobian), whose outputs
+// are solve_system's inputs.  Everything is validated on the host before the
+// launch; the index range check costs one reduction and one sync (the LM loop
+// of dpvo_amd/loop_closure.py syncs every iteration anyway).
+std::vector<torch::Tensor> ba_pgo_residual(torch::Tensor Ginv, torch::Tensor C, torch::Tensor ii,
+                                           torch::Tensor jj, bool jacobian) {
+  check_device(Ginv, "Ginv");
+  check_device(C, "C");
+  TORCH_CHECK(Ginv.scalar_type() == torch::kFloat32 || Ginv.scalar_type() == torch::kFloat64,
+              "cuda_ba.pgo_residual: Ginv must be float32 or float64");
+  TORCH_CHECK(C.scalar_type() == Ginv.scalar_type(),
+              "cuda_ba.pgo_residual: Ginv and C must have the same dtype");
+  TORCH_CHECK(Ginv.dim() == 2 && Ginv.size(1) == 7, "cuda_ba.pgo_residual: Ginv must be [n, 7]");
+  TORCH_CHECK(C.dim() == 2 && C.size(1) == 8, "cuda_ba.pgo_residual: C must be [r, 8]");
+  ii = idx64(ii, "ii");
+  jj = idx64(jj, "jj");
+  const int64_t n = Ginv.size(0), r = C.size(0);
+  TORCH_CHECK(ii.dim() == 1 && jj.dim() == 1 && ii.numel() == r && jj.numel() == r,
+              "cuda_ba.pgo_residual: ii / jj must be [r]");
+  TORCH_CHECK(Ginv.device() == C.device() && ii.device() == C.device() &&
+                  jj.device() == C.device(),
+              "cuda_ba.pgo_residual: tensors on different devices");
+  TORCH_CHECK(r <= (1 << 26) && n < (1LL << 31), "cuda_ba.pgo_residual: graph too large");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(Ginv.device());
+  Ginv = Ginv.contiguous();
+  C = C.contiguous();
+  auto res = torch::empty({r, 7}, Ginv.options());
+  torch::Tensor Ji, Jj;
+  if (jacobian) {
+    Ji = torch::empty({r, 7, 7}, Ginv.options());
+    Jj = torch::empty({r, 7, 7}, Ginv.options());
+  }
+  if (r > 0) {
+    const auto mm = at::aminmax(torch::cat({ii, jj}));
+    const auto mmh = torch::stack({std::get<0>(mm), std::get<1>(mm)}).cpu();
+    const int64_t lo = mmh.data_ptr<int64_t>()[0], hi = mmh.data_ptr<int64_t>()[1];
+    TORCH_CHECK(lo >= 0 && hi < n, "cuda_ba.pgo_residual: pose index out of range [0, ", n,
+                "): min ", lo, ", max ", hi);
+    check_status(dpvo_pgo_residual(Ginv.data_ptr(), C.data_ptr(), ii.data_ptr<int64_t>(),
+                                   jj.data_ptr<int64_t>(), (int)r, (int)n, dtype_code(Ginv),
+                                   res.data_ptr(), jacobian ? Ji.data_ptr() : nullptr,
+                                   jacobian ? Jj.data_ptr() : nullptr, current_stream()),
+                 "cuda_ba.pgo_residual");
+  }
+  if (jacobian) return {res, Ji, Jj};
+  return {res};
+}
+
 // Split F-BA for the edge-sharded multi-GPU path.
 torch::Tensor ba_setup(torch::Tensor ii, torch::Tensor jj, torch::Tensor kk, int num_patches,
                        int t0, int t1) {
@@ -1043,6 +1092,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("neighbors", &ba_neighbors, "temporal neighboor indicies");
   m.def("reproject", &ba_reproject, "temporal neighboor indicies");
   m.def("solve_system", &ba_solve_system, "Sim3 pose-graph solve (ba.cpp:120-180)");
+  m.def("pgo_residual", &ba_pgo_residual, "Sim3 pose-graph residual and Jacobians, one launch",
+        py::arg("Ginv"), py::arg("C"), py::arg("ii"), py::arg("jj"), py::arg("jacobian") = false);
   // additions: split BA for the sharded multi-GPU path
   m.def("setup", &ba_setup, "BA graph setup -> workspace");
   m.def("build_schur", &ba_build_schur, "linearize + Schur complement (S_lower, y)");

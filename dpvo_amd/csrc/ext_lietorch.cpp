@@ -1,7 +1,8 @@
 // ext_lietorch.cpp -- the `lietorch_backends` extension module (drop-in for
 // dpvo/lietorch/src/lietorch.cpp:286-316), bound to the C ABI in dpvo_hot.h.
-// Group ids follow dispatch.h:24-45; this build implements SO3 (1) and SE3 (3),
-// the groups on DPVO's hot path.
+// Group ids follow dispatch.h:24-45; this build implements SO3 (1), SE3 (3),
+// the groups on DPVO's hot path, and Sim3 (4), the group of the loop-closure
+// pose graph.  RxSO3 (2) is not built: nothing in DPVO uses it on its own.
 #include "ext_common.hpp"
 
 using namespace dpvo_ext;
@@ -10,11 +11,11 @@ enum { OP_EXP = 0, OP_LOG, OP_INV, OP_MUL, OP_ADJ, OP_ADJT, OP_ACT, OP_ACT4, OP_
        OP_JINV };
 
 static void check_group(int g) {
-  TORCH_CHECK(g == 1 || g == 3, "lietorch_backends: group ", g,
-              " not supported by the MI355X build (SO3=1, SE3=3 implemented)");
+  TORCH_CHECK(g == 1 || g == 3 || g == 4, "lietorch_backends: group ", g,
+              " not supported by the MI355X build (SO3=1, SE3=3, Sim3=4 implemented)");
 }
-static int K_of(int g) { return g == 1 ? 3 : 6; }
-static int N_of(int g) { return g == 1 ? 4 : 7; }
+static int K_of(int g) { return g == 1 ? 3 : g == 3 ? 6 : 7; }
+static int N_of(int g) { return K_of(g) + 1; }
 
 // lietorch.cpp:7 CHECK_CONTIGUOUS
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")

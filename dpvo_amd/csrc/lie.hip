@@ -1,11 +1,15 @@
-// lie.hip -- lietorch SO3 (group 1) / SE3 (group 3) on gfx950 (L-SE3).
+// lie.hip -- lietorch SO3 (group 1) / SE3 (group 3) / Sim3 (group 4) on gfx950
+// (L-SE3).  The Sim3 math lives in sim3.hpp (shared with pgo.hip).
 //
 // Reference semantics: dpvo/lietorch/include/so3.h, se3.h and the kernels of
 // dpvo/lietorch/src/lietorch_gpu.cu:20-294 (one thread per group element,
 // Eigen math).  Restated here without Eigen: plain fixed-size register math,
 // templated on float/double, quaternion (x, y, z, w) normalised on load
 // (so3.h:95-97), tangent ordering (tau, phi).
+#include <type_traits>
+
 #include "common.hpp"
+#include "sim3.hpp"
 
 namespace dpvo {
 namespace lie {
@@ -514,8 +518,11 @@ struct Dims {
   int xin, yin, out, gin, o0, o1;
 };
 
+__host__ __device__ constexpr int dim_K(int group) { return group == 1 ? 3 : group == 3 ? 6 : 7; }
+__host__ __device__ constexpr int dim_N(int group) { return dim_K(group) + 1; }
+
 __host__ __device__ constexpr Dims fwd_dims(int group, int op) {
-  const int K = group == 1 ? 3 : 6, N = group == 1 ? 4 : 7;
+  const int K = dim_K(group), N = dim_N(group);
   return op == OP_EXP    ? Dims{K, 0, N, 0, 0, 0}
          : op == OP_LOG  ? Dims{N, 0, K, 0, 0, 0}
          : op == OP_INV  ? Dims{N, 0, N, 0, 0, 0}
@@ -527,7 +534,7 @@ __host__ __device__ constexpr Dims fwd_dims(int group, int op) {
                          : Dims{N, K, K, 0, 0, 0};  // ADJ, ADJT, JINV
 }
 __host__ __device__ constexpr Dims bwd_dims(int group, int op) {
-  const int K = group == 1 ? 3 : 6, N = group == 1 ? 4 : 7;
+  const int K = dim_K(group), N = dim_N(group);
   return op == OP_EXP    ? Dims{K, 0, 0, N, K, 0}
          : op == OP_LOG  ? Dims{N, 0, 0, K, N, 0}
          : op == OP_INV  ? Dims{N, 0, 0, N, N, 0}
@@ -539,22 +546,28 @@ __host__ __device__ constexpr Dims bwd_dims(int group, int op) {
 
 // One thread per group element; (group, op) are template parameters so every
 // loop bound is a compile-time constant and the operands stay in registers.
+// Sim3 (G == 4) computes in fp64 whatever the tensors' dtype (sim3.hpp).
+template <typename S, int G>
+using Compute = typename std::conditional<G == 4, double, S>::type;
+
 template <typename S, int G, int OP>
 __global__ void __launch_bounds__(256)
     lie_fwd_kernel(int n, const S* __restrict__ X, const S* __restrict__ Y, S* __restrict__ out) {
   constexpr Dims d = fwd_dims(G, OP);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    S x[7], y[7], o[49];
+    Compute<S, G> x[8], y[8], o[64];
 #pragma unroll
     for (int k = 0; k < d.xin; k++) x[k] = X[(size_t)i * d.xin + k];
 #pragma unroll
     for (int k = 0; k < d.yin; k++) y[k] = Y[(size_t)i * d.yin + k];
-    if constexpr (G == 3)
+    if constexpr (G == 4)
+      sim3::fwd(OP, x, y, o);
+    else if constexpr (G == 3)
       se3_fwd<S>(OP, x, y, o);
     else
       so3_fwd<S>(OP, x, y, o);
 #pragma unroll
-    for (int k = 0; k < d.out; k++) out[(size_t)i * d.out + k] = o[k];
+    for (int k = 0; k < d.out; k++) out[(size_t)i * d.out + k] = (S)o[k];
   }
 }
 
@@ -563,11 +576,11 @@ __global__ void __launch_bounds__(256)
     lie_bwd_kernel(int n, const S* __restrict__ Gr, const S* __restrict__ X,
                    const S* __restrict__ Y, S* __restrict__ o0, S* __restrict__ o1) {
   constexpr Dims d = bwd_dims(G, OP);
-  constexpr int K = G == 1 ? 3 : 6;
+  constexpr int K = dim_K(G);
   // gradient rows of group elements are N-strided, their first K entries used
   constexpr int gread = (OP == OP_EXP || OP == OP_INV || OP == OP_MUL) ? K : d.gin;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    S x[7], y[7], g[7], a[7], b[7];
+    Compute<S, G> x[8], y[8], g[8], a[8], b[8];
 #pragma unroll
     for (int k = 0; k < d.xin; k++) x[k] = X[(size_t)i * d.xin + k];
 #pragma unroll
@@ -575,15 +588,17 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int k = 0; k < gread; k++) g[k] = Gr[(size_t)i * d.gin + k];
 #pragma unroll
-    for (int k = 0; k < 7; k++) a[k] = b[k] = 0;
-    if constexpr (G == 3)
+    for (int k = 0; k < 8; k++) a[k] = b[k] = 0;
+    if constexpr (G == 4)
+      sim3::bwd(OP, g, x, y, a, b);
+    else if constexpr (G == 3)
       se3_bwd<S>(OP, g, x, y, a, b);
     else
       so3_bwd<S>(OP, g, x, y, a, b);
 #pragma unroll
-    for (int k = 0; k < d.o0; k++) o0[(size_t)i * d.o0 + k] = a[k];
+    for (int k = 0; k < d.o0; k++) o0[(size_t)i * d.o0 + k] = (S)a[k];
 #pragma unroll
-    for (int k = 0; k < d.o1; k++) o1[(size_t)i * d.o1 + k] = b[k];
+    for (int k = 0; k < d.o1; k++) o1[(size_t)i * d.o1 + k] = (S)b[k];
   }
 }
 
@@ -635,34 +650,38 @@ static unsigned lie_grid(int n) {
 
 DPVO_EXPORT int dpvo_lie_forward(int group, int op, int dtype, int n, const void* X, const void* Y,
                                  void* out, void* stream) {
-  if (group != 1 && group != 3) return DPVO_ERR_UNSUPPORTED;
+  if (group != 1 && group != 3 && group != 4) return DPVO_ERR_UNSUPPORTED;  // 2 = RxSO3
   if (op < 0 || op > lie::OP_JINV || n < 0) return DPVO_ERR_INVALID;
   if (n == 0) return DPVO_OK;
   hipStream_t s = as_stream(stream);
   const unsigned g = lie_grid(n);
   if (dtype == DPVO_F32)
-    return group == 3 ? lie::launch_fwd<float, 3>(op, n, X, Y, out, s, g)
-                      : lie::launch_fwd<float, 1>(op, n, X, Y, out, s, g);
+    return group == 4   ? lie::launch_fwd<float, 4>(op, n, X, Y, out, s, g)
+           : group == 3 ? lie::launch_fwd<float, 3>(op, n, X, Y, out, s, g)
+                        : lie::launch_fwd<float, 1>(op, n, X, Y, out, s, g);
   if (dtype == DPVO_F64)
-    return group == 3 ? lie::launch_fwd<double, 3>(op, n, X, Y, out, s, g)
-                      : lie::launch_fwd<double, 1>(op, n, X, Y, out, s, g);
+    return group == 4   ? lie::launch_fwd<double, 4>(op, n, X, Y, out, s, g)
+           : group == 3 ? lie::launch_fwd<double, 3>(op, n, X, Y, out, s, g)
+                        : lie::launch_fwd<double, 1>(op, n, X, Y, out, s, g);
   return DPVO_ERR_UNSUPPORTED;
 }
 
 DPVO_EXPORT int dpvo_lie_backward(int group, int op, int dtype, int n, const void* grad,
                                   const void* X, const void* Y, void* out0, void* out1,
                                   void* stream) {
-  if (group != 1 && group != 3) return DPVO_ERR_UNSUPPORTED;
+  if (group != 1 && group != 3 && group != 4) return DPVO_ERR_UNSUPPORTED;  // 2 = RxSO3
   if (op < 0 || op > lie::OP_ACT4 || n < 0) return DPVO_ERR_INVALID;
   if (n == 0) return DPVO_OK;
   hipStream_t s = as_stream(stream);
   const unsigned g = lie_grid(n);
   if (dtype == DPVO_F32)
-    return group == 3 ? lie::launch_bwd<float, 3>(op, n, grad, X, Y, out0, out1, s, g)
-                      : lie::launch_bwd<float, 1>(op, n, grad, X, Y, out0, out1, s, g);
+    return group == 4   ? lie::launch_bwd<float, 4>(op, n, grad, X, Y, out0, out1, s, g)
+           : group == 3 ? lie::launch_bwd<float, 3>(op, n, grad, X, Y, out0, out1, s, g)
+                        : lie::launch_bwd<float, 1>(op, n, grad, X, Y, out0, out1, s, g);
   if (dtype == DPVO_F64)
-    return group == 3 ? lie::launch_bwd<double, 3>(op, n, grad, X, Y, out0, out1, s, g)
-                      : lie::launch_bwd<double, 1>(op, n, grad, X, Y, out0, out1, s, g);
+    return group == 4   ? lie::launch_bwd<double, 4>(op, n, grad, X, Y, out0, out1, s, g)
+           : group == 3 ? lie::launch_bwd<double, 3>(op, n, grad, X, Y, out0, out1, s, g)
+                        : lie::launch_bwd<double, 1>(op, n, grad, X, Y, out0, out1, s, g);
   return DPVO_ERR_UNSUPPORTED;
 }
 

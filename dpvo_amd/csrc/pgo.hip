@@ -11,6 +11,7 @@
 // dense layout costs 392 n^2 bytes (n = 4096 poses: 6.6 GB, comfortably
 // resident in 288 GB) and hands a plain SPD matrix to the device Cholesky.
 #include "common.hpp"
+#include "sim3.hpp"
 
 namespace dpvo {
 namespace {
@@ -581,4 +582,123 @@ DPVO_EXPORT int dpvo_pgo_back(const int64_t* plan, const int64_t* hdr, const dou
     hipLaunchKernelGGL(pgo_segment_backward_kernel, dim3((unsigned)hdr[hNseg]), dim3(64), 0,
                        (hipStream_t)stream_, plan, xB, ws);
   return launch_status();
+}
+
+// ---------------------------------------------------------------------------
+// Pose-graph residual and Jacobians (optim_utils.py:152-189, where PyPose and
+// torch.autograd.functional.jacobian produce them on the CPU).  For edge e
+//   res[e] = Log(C[e] Exp(Ginv[ii[e]]) Exp(Ginv[jj[e]])^-1),
+// J_i[e] = d res / d Ginv[ii[e]], J_j[e] = d res / d Ginv[jj[e]], both
+// [residual component][pose dof]: the blocks dpvo_pgo_factor reads.
+//
+// One launch, 16 lanes per edge (4 edges per wave).  Lane l < 14 carries one
+// forward-mode direction through the fp64 Sim3 code of sim3.hpp -- component
+// l of Ginv[ii] for l < 7, component l - 7 of Ginv[jj] otherwise -- and stores
+// one column of one Jacobian; lane 14 stores the residual (the value part,
+// identical in every lane); lane 15 idles.  The Jacobians are therefore the
+// derivative of the code that computes the residual, exact at sigma = 0 and
+// theta = 0.  One direction per lane keeps a lane at two doubles per scalar;
+// seven directions per lane would spill.  No LDS, no atomics; adjacent lanes
+// store adjacent Jacobian columns.
+
+namespace dpvo {
+namespace {
+
+constexpr int kEdgeLanes = 16;
+constexpr int kResidualBlock = 256;
+
+template <typename S>
+__global__ void __launch_bounds__(kResidualBlock)
+    pgo_residual_jac_kernel(const S* __restrict__ Ginv, const S* __restrict__ C,
+                            const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int r,
+                            int n, S* __restrict__ res, S* __restrict__ Ji, S* __restrict__ Jj) {
+  using sim3::Dual;
+  const int64_t tid = (int64_t)blockIdx.x * kResidualBlock + threadIdx.x;
+  const int64_t e = tid / kEdgeLanes;
+  const int l = (int)(tid % kEdgeLanes);
+  if (e >= r || l == 15) return;
+  const int64_t pi = ii[e], pj = jj[e];
+  if (pi < 0 || pi >= n || pj < 0 || pj >= n) return;  // callers validate; never read outside Ginv
+  double c[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) c[k] = (double)C[e * 8 + k];
+  const sim3::Elem<double> Cv = sim3::load(c);
+  sim3::Elem<Dual> Cd;
+#pragma unroll
+  for (int k = 0; k < 3; k++) Cd.t[k] = Dual(Cv.t[k]);
+#pragma unroll
+  for (int k = 0; k < 4; k++) Cd.q[k] = Dual(Cv.q[k]);
+  Cd.s = Dual(Cv.s);
+  Dual gi[7], gj[7], o[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    gi[k] = Dual((double)Ginv[pi * 7 + k], l == k ? 1.0 : 0.0);
+    gj[k] = Dual((double)Ginv[pj * 7 + k], l == 7 + k ? 1.0 : 0.0);
+  }
+  sim3::pgo_edge<Dual>(Cd, gi, gj, o);
+  if (l == 14) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) res[e * 7 + k] = (S)o[k].v;
+  } else {
+    S* J = (l < 7 ? Ji : Jj) + e * 49 + (l < 7 ? l : l - 7);
+#pragma unroll
+    for (int k = 0; k < 7; k++) J[k * 7] = (S)o[k].d;
+  }
+}
+
+// residual only: one lane per edge, the same code on plain doubles (the same
+// IEEE operations as the value parts above: bit-identical residuals)
+template <typename S>
+__global__ void __launch_bounds__(kResidualBlock)
+    pgo_residual_kernel(const S* __restrict__ Ginv, const S* __restrict__ C,
+                        const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int r,
+                        int n, S* __restrict__ res) {
+  const int64_t e = (int64_t)blockIdx.x * kResidualBlock + threadIdx.x;
+  if (e >= r) return;
+  const int64_t pi = ii[e], pj = jj[e];
+  if (pi < 0 || pi >= n || pj < 0 || pj >= n) return;
+  double c[8], gi[7], gj[7], o[7];
+#pragma unroll
+  for (int k = 0; k < 8; k++) c[k] = (double)C[e * 8 + k];
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    gi[k] = (double)Ginv[pi * 7 + k];
+    gj[k] = (double)Ginv[pj * 7 + k];
+  }
+  sim3::pgo_edge<double>(sim3::load(c), gi, gj, o);
+#pragma unroll
+  for (int k = 0; k < 7; k++) res[e * 7 + k] = (S)o[k];
+}
+
+template <typename S>
+int launch_residual(const void* Ginv, const void* C, const int64_t* ii, const int64_t* jj, int r,
+                    int n, void* res, void* Ji, void* Jj, hipStream_t stream) {
+  if (Ji) {
+    const int64_t blocks = ((int64_t)r * kEdgeLanes + kResidualBlock - 1) / kResidualBlock;
+    hipLaunchKernelGGL((pgo_residual_jac_kernel<S>), dim3((unsigned)blocks), dim3(kResidualBlock),
+                       0, stream, (const S*)Ginv, (const S*)C, ii, jj, r, n, (S*)res, (S*)Ji,
+                       (S*)Jj);
+  } else {
+    hipLaunchKernelGGL((pgo_residual_kernel<S>),
+                       dim3((unsigned)((r + kResidualBlock - 1) / kResidualBlock)),
+                       dim3(kResidualBlock), 0, stream, (const S*)Ginv, (const S*)C, ii, jj, r, n,
+                       (S*)res);
+  }
+  return launch_status();
+}
+
+}  // namespace
+}  // namespace dpvo
+
+DPVO_EXPORT int dpvo_pgo_residual(const void* Ginv, const void* C, const int64_t* ii,
+                                  const int64_t* jj, int r, int n, int dtype, void* res, void* J_i,
+                                  void* J_j, void* stream) {
+  if (r < 0 || n < 0 || (J_i == nullptr) != (J_j == nullptr)) return DPVO_ERR_INVALID;
+  if (r > (1 << 26)) return DPVO_ERR_UNSUPPORTED;
+  if (r == 0) return DPVO_OK;
+  if (!Ginv || !C || !ii || !jj || !res || n == 0) return DPVO_ERR_INVALID;
+  hipStream_t s = as_stream(stream);
+  if (dtype == DPVO_F32) return launch_residual<float>(Ginv, C, ii, jj, r, n, res, J_i, J_j, s);
+  if (dtype == DPVO_F64) return launch_residual<double>(Ginv, C, ii, jj, r, n, res, J_i, J_j, s);
+  return DPVO_ERR_UNSUPPORTED;
 }

@@ -5,7 +5,8 @@ broadcasting.py:5-31 (cuteboyqq/DPVO); the arithmetic runs in the HIP kernels
 of `lietorch_backends` (dpvo_amd/csrc/lie.hip).
 
 Conventions (reference): SE3 data = (tx, ty, tz, qx, qy, qz, qw); tangent =
-(tau, phi); gradients w.r.t. a group element live in the tangent space,
+(tau, phi); Sim3 appends the scale s to the data and sigma = log s to the
+tangent; gradients w.r.t. a group element live in the tangent space,
 carried in an embedding-sized row whose first K entries are used.
 """
 from __future__ import annotations
@@ -328,27 +329,38 @@ class SE3(LieGroup):
         return SE3(torch.cat([t * s.unsqueeze(-1), q], dim=-1))
 
 
-class _Unsupported(LieGroup):
-    def __init__(self, data):
-        raise NotImplementedError(
-            f"{self.group_name} (lietorch group id {self.group_id}) is not part of the MI355X "
-            "build: DPVO's per-frame hot path uses SE3 only (SURVEY 8a L-SE3)")
-
-
-class RxSO3(_Unsupported):
+class RxSO3(LieGroup):
     group_name = "RxSO3"
     group_id = 2
     manifold_dim = 4
     embedded_dim = 5
     id_elem = torch.as_tensor([0.0, 0.0, 0.0, 1.0, 1.0])
 
+    def __init__(self, data):
+        raise NotImplementedError(
+            f"{self.group_name} (lietorch group id {self.group_id}) is not part of the MI355X "
+            "build: DPVO uses SO3, SE3 and Sim3 only")
 
-class Sim3(_Unsupported):
+
+class Sim3(LieGroup):
+    """Similarity transforms, data (tx, ty, tz, qx, qy, qz, qw, s): the group of
+    the loop-closure pose graph (dpvo/lietorch/groups.py:296-322)."""
+
     group_name = "Sim3"
     group_id = 4
     manifold_dim = 7
     embedded_dim = 8
     id_elem = torch.as_tensor([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 1.0])
+
+    def __init__(self, data):
+        if isinstance(data, SO3):
+            data = torch.cat([torch.zeros_like(data.data[..., :3]), data.data,
+                              torch.ones_like(data.data[..., :1])], -1)
+        elif isinstance(data, SE3):
+            data = torch.cat([data.data, torch.ones_like(data.data[..., :1])], -1)
+        elif isinstance(data, Sim3):
+            data = data.data
+        super().__init__(data)
 
 
 def cat(group_list, dim):

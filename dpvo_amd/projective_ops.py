@@ -67,8 +67,11 @@ def transform(poses, patches, intrinsics, ii, jj, kk, depth=False, valid=False, 
                               o, H, o, -Z, o, X,
                               o, o, H, Y, -X, o,
                               o, o, o, o, o, o], dim=-1).view(1, len(ii), 4, 6)
-        elif isinstance(Gij, Sim3):  # pragma: no cover - Sim3 is not built
-            raise NotImplementedError("Sim3 transform")
+        elif isinstance(Gij, Sim3):  # the extra column is the scale generator's (X, Y, Z, 0)
+            Ja = torch.stack([H, o, o, o, Z, -Y, X,
+                              o, H, o, -Z, o, X, Y,
+                              o, o, H, Y, -X, o, Z,
+                              o, o, o, o, o, o, o], dim=-1).view(1, len(ii), 4, 7)
         Jp = torch.stack([fx * d, o, -fx * X * d * d, o,
                           o, fy * d, -fy * Y * d * d, o], dim=-1).view(1, len(ii), 2, 4)
         Jj = torch.matmul(Jp, Ja)

@@ -161,6 +161,21 @@ int dpvo_pgo_assemble(const float* J_Ginv_i, const float* J_Ginv_j, const int64_
                       const int64_t* jj, const float* res, int r, int n, float ep, float lm,
                       double* A, double* b, void* stream);
 
+/* Residual and Jacobians of every pose-graph edge in one launch (replaces the
+   PyPose + autograd evaluation of dpvo/loop_closure/optim_utils.py:152-189).
+   Ginv [n, 7]: tangent of each world-to-camera Sim3 pose; C [r, 8]: Sim3 data
+   (t, q, s) of each edge's measured relative transform; ii / jj [r] int64 in
+   [0, n) (the caller validates them; an edge outside the range is skipped).
+     res[e] = Log(C[e] Exp(Ginv[ii[e]]) Exp(Ginv[jj[e]])^-1)           [r, 7]
+     J_i[e] = d res[e] / d Ginv[ii[e]], J_j[e] = d res[e] / d Ginv[jj[e]]
+              [r, 7, 7] = [edge, residual component, pose dof]
+   J_i and J_j are both given or both NULL (residual only; the residual is
+   bit-identical either way).  Plain derivatives with respect to the 7 tangent
+   numbers, exact (forward mode), finite at sigma = 0 and theta = 0.  dtype
+   DPVO_F32 / DPVO_F64 is that of every floating tensor; arithmetic is fp64. */
+int dpvo_pgo_residual(const void* Ginv, const void* C, const int64_t* ii, const int64_t* jj,
+                      int r, int n, int dtype, void* res, void* J_i, void* J_j, void* stream);
+
 /* Structured sparse solve of the same system (the default path of
    cuda_ba.solve_system, replacing Eigen SimplicialCholesky, ba.cpp:99-180).
    Poses touched by a long edge (|i - j| > 1) form a dense "border"; the other
@@ -385,7 +400,11 @@ int dpvo_neighbors(const int64_t* ii, const int64_t* jj, int E, int64_t* ix, int
 
 /* L-SE3.  Replaces lietorch_backends.{expm, logm, inv, mul, adj, adjT, act,
    act4, as_matrix, projector, Jinv} (dpvo/lietorch/src/lietorch.cpp:18-283,
-   lietorch_gpu.cu:20-601).  group: 1 = SO3, 3 = SE3 (dispatch.h:24-45).
+   lietorch_gpu.cu:20-601).  group: 1 = SO3, 3 = SE3, 4 = Sim3 (dispatch.h:24-45;
+   2 = RxSO3 is DPVO_ERR_UNSUPPORTED).  Sim3: data (t, q, s), N = 8, tangent
+   (tau, phi, sigma), K = 7, arithmetic in fp64 for both dtypes, and Jinv and
+   the Exp / Log gradients use the exact left Jacobian (the derivative of the
+   forward map), not the reference's truncated series (sim3.h:167-191).
    dtype DPVO_F32 / DPVO_F64.  n elements, each row contiguous:
      op 0 exp   : X=a[K]          -> out[N]
      op 1 log   : X[N]            -> out[K]
