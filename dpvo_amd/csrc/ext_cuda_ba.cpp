@@ -685,6 +685,66 @@ std::vector<torch::Tensor> ba_pgo_residual(torch::Tensor Ginv, torch::Tensor C, 
   return {res};
 }
 
+// RANSAC-Umeyama estimate of a loop measurement (optim_utils.py:64-150) in two
+// launches: [model f64[21], info i32[4], mask bool[N]] of dpvo_ransac_umeyama
+// (+ counts i32[H], the score of every hypothesis, with return_counts).
+// check_samples: the range check of `samples` costs one aminmax and one host
+// read, as pgo_residual's; without it (the caller drew the samples itself, or
+// the stream is being captured) the call makes no sync, and a sample outside
+// [0, N) only makes its hypothesis degenerate.
+std::vector<torch::Tensor> ba_ransac_umeyama(torch::Tensor src, torch::Tensor dst,
+                                             torch::Tensor samples, double threshold,
+                                             int64_t early_exit, bool check_samples,
+                                             bool return_counts) {
+  TORCH_CHECK(src.is_cuda() && dst.is_cuda() && samples.is_cuda(),
+              "cuda_ba.ransac_umeyama: src, dst and samples must be GPU (HIP) tensors; the "
+              "MI355X build has no CPU path");
+  TORCH_CHECK(src.scalar_type() == torch::kFloat32 || src.scalar_type() == torch::kFloat64,
+              "cuda_ba.ransac_umeyama: src must be float32 or float64");
+  TORCH_CHECK(dst.scalar_type() == src.scalar_type(),
+              "cuda_ba.ransac_umeyama: src and dst must have the same dtype");
+  TORCH_CHECK(src.dim() == 2 && src.size(1) == 3 && dst.dim() == 2 && dst.size(1) == 3 &&
+                  src.size(0) == dst.size(0),
+              "cuda_ba.ransac_umeyama: src and dst must both be [N, 3]");
+  TORCH_CHECK(samples.scalar_type() == torch::kInt32 || samples.scalar_type() == torch::kInt64,
+              "cuda_ba.ransac_umeyama: samples must be int32 or int64");
+  TORCH_CHECK(samples.dim() == 2 && samples.size(1) == 3 && samples.size(0) >= 1,
+              "cuda_ba.ransac_umeyama: samples must be [H, 3] with H >= 1");
+  TORCH_CHECK(src.device() == dst.device() && src.device() == samples.device(),
+              "cuda_ba.ransac_umeyama: tensors on different devices");
+  const int64_t N = src.size(0), H = samples.size(0);
+  TORCH_CHECK(N >= 3, "cuda_ba.ransac_umeyama: needs N >= 3 points, got ", N);
+  TORCH_CHECK(N <= (1 << 28) && H <= (1 << 24), "cuda_ba.ransac_umeyama: problem too large");
+  TORCH_CHECK(threshold > 0.0, "cuda_ba.ransac_umeyama: threshold must be positive");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+  if (check_samples && !is_capturing()) {
+    const auto mm = at::aminmax(samples);
+    const auto mmh = torch::stack({std::get<0>(mm), std::get<1>(mm)}).to(torch::kInt64).cpu();
+    const int64_t lo = mmh.data_ptr<int64_t>()[0], hi = mmh.data_ptr<int64_t>()[1];
+    TORCH_CHECK(lo >= 0 && hi < N, "cuda_ba.ransac_umeyama: sample index out of range [0, ", N,
+                "): min ", lo, ", max ", hi);
+  }
+  src = src.contiguous();
+  dst = dst.contiguous();
+  samples = samples.to(torch::kInt32).contiguous();
+  const auto i32 = src.options().dtype(torch::kInt32);
+  auto model = torch::empty({21}, src.options().dtype(torch::kFloat64));
+  auto info = torch::empty({4}, i32);
+  auto mask = torch::empty({N}, src.options().dtype(torch::kBool));
+  const size_t wsb = dpvo_ransac_umeyama_workspace_bytes((int)N, (int)H);
+  auto ws = torch::empty({(int64_t)(wsb / sizeof(int32_t))}, i32);
+  early_exit = std::min<int64_t>(std::max<int64_t>(early_exit, INT32_MIN), INT32_MAX);
+  check_status(dpvo_ransac_umeyama(src.data_ptr(), dst.data_ptr(), (int)N, dtype_code(src),
+                                   samples.data_ptr<int32_t>(), (int)H, threshold,
+                                   (int)early_exit, model.data_ptr<double>(),
+                                   info.data_ptr<int32_t>(),
+                                   reinterpret_cast<uint8_t*>(mask.data_ptr<bool>()),
+                                   ws.data_ptr(), wsb, current_stream()),
+               "cuda_ba.ransac_umeyama");
+  if (return_counts) return {model, info, mask, ws.narrow(0, 0, H)};
+  return {model, info, mask};
+}
+
 // Split F-BA for the edge-sharded multi-GPU path.
 torch::Tensor ba_setup(torch::Tensor ii, torch::Tensor jj, torch::Tensor kk, int num_patches,
                        int t0, int t1) {
@@ -1094,6 +1154,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("solve_system", &ba_solve_system, "Sim3 pose-graph solve (ba.cpp:120-180)");
   m.def("pgo_residual", &ba_pgo_residual, "Sim3 pose-graph residual and Jacobians, one launch",
         py::arg("Ginv"), py::arg("C"), py::arg("ii"), py::arg("jj"), py::arg("jacobian") = false);
+  m.def("ransac_umeyama", &ba_ransac_umeyama,
+        "RANSAC-Umeyama Sim3 estimate from matched points, two launches", py::arg("src"),
+        py::arg("dst"), py::arg("samples"), py::arg("threshold"), py::arg("early_exit"),
+        py::arg("check_samples") = true, py::arg("return_counts") = false);
   // additions: split BA for the sharded multi-GPU path
   m.def("setup", &ba_setup, "BA graph setup -> workspace");
   m.def("build_schur", &ba_build_schur, "linearize + Schur complement (S_lower, y)");

@@ -1,20 +1,39 @@
-"""Loop-closure pose-graph optimisation on the device (P-PGO).
+"""Long-term loop closure on the device, from matched 3-D points to the
+corrected map.
 
-Restates dpvo/loop_closure/optim_utils.py:15-17, 158-243 (cuteboyqq/DPVO) on
-device tensors.  The reference evaluates the residuals and their Jacobians
-with PyPose Sim3 and torch.autograd.functional.jacobian on the CPU, in a
-worker process; here one HIP kernel (`cuda_ba.pgo_residual`, pgo.hip) produces
-residual and both 7x7 Jacobians of every edge, `cuda_ba.solve_system` solves
-the damped normal equations, and `dpvo_amd.lietorch.Sim3` holds the poses.
+Restates dpvo/loop_closure/optim_utils.py:15-17, 64-150, 158-243 and
+dpvo/loop_closure/long_term.py:175-203, 235-266 (cuteboyqq/DPVO) on device
+tensors:
 
-Retrieval, keypoint matching and the Umeyama / RANSAC estimate of the loop
-measurements are not part of this module: `run_pgo` starts from the loop
-edges (`loop_ii`, `loop_jj`) and their measured Sim3 transforms.
+  `ransac_umeyama`  the Sim3 measurement of a loop from two matched point
+                    clouds: 3-point Umeyama hypotheses scored concurrently and
+                    the refit on the winner's inliers, two launches
+                    (`cuda_ba.ransac_umeyama`, ransac.hip; the reference is
+                    numba on the CPU over points copied off the GPU);
+  `close_loop`      that measurement joined with the earlier loops and handed
+                    to `run_pgo` (the second half of
+                    LongTermLoopClosure.close_loop);
+  `run_pgo`         the Sim3 pose-graph LM.  The reference evaluates residuals
+                    and Jacobians with PyPose Sim3 and
+                    torch.autograd.functional.jacobian on the CPU, in a worker
+                    process; here one HIP kernel (`cuda_ba.pgo_residual`,
+                    pgo.hip) produces residual and both 7x7 Jacobians of every
+                    edge, `cuda_ba.solve_system` solves the damped normal
+                    equations, and `dpvo_amd.lietorch.Sim3` holds the poses;
+  `apply_result`    the optimised poses and scales written back to the map
+                    (lc_callback and _rescale_deltas).
+
+Retrieval (DBoW2) and keypoint detection / matching (DISK, LightGlue) are not
+part of this module: `close_loop` starts from the frame pair (i, j) and its
+two arrays of matched 3-D points, which a caller's own matcher provides.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
+from . import global_ba
 from .fastba import cuda_ba
 from .lietorch import SE3, Sim3
 
@@ -131,3 +150,144 @@ def split_result(final):
     (long_term.py:196-200)."""
     res, s = _sim3_data(final).split([7, 1], dim=-1)
     return SE3(res).inv().data, s.squeeze(-1)
+
+
+class Sim3Estimate(NamedTuple):
+    """Result of `ransac_umeyama`, device tensors: dst ~ s R src + t."""
+    R: torch.Tensor            # [3, 3]
+    t: torch.Tensor            # [3]
+    s: torch.Tensor            # []
+    sim3: torch.Tensor         # [8] lietorch data (t, q xyzw with qw >= 0, s)
+    num_inliers: torch.Tensor  # [] int32
+    mask: torch.Tensor         # [N] bool, inliers of the winning hypothesis
+    hypothesis: torch.Tensor   # [] int32, index of the winning sample (-1: none)
+    status: torch.Tensor       # [] int32, 0 ok / 1 no inliers / 2 degenerate refit
+    info: torch.Tensor         # [4] int32 (num_inliers, hypothesis, stop index, status)
+
+
+def draw_samples(N, iterations, device, generator=None):
+    """[iterations, 3] int32 uniform triples of distinct indices in [0, N):
+    the three smallest of N uniform numbers per row."""
+    u = torch.rand(iterations, N, device=device, generator=generator)
+    return u.argsort(dim=1)[:, :3].to(torch.int32)
+
+
+def ransac_umeyama(src_points, dst_points, iterations=1, threshold=0.1, samples=None,
+                   generator=None, early_exit=100):
+    """RANSAC over 3-point Umeyama models and the refit on the winner's inliers
+    (optim_utils.py:117-150), dst ~ s R src + t, on the device.
+
+    src_points / dst_points [N, 3] float32 or float64 (the arithmetic is fp64
+    either way).  samples [H, 3]: the point triples to try, in the order the
+    reference's loop would draw them; with samples=None, `iterations` uniform
+    triples of distinct indices are drawn on the device from `generator` (a
+    device torch.Generator, or the default one).  The reference draws with an
+    unseeded np.random.choice, so what is reproduced is the distribution of
+    the samples, not their stream.  Given the samples, the result is the
+    reference's: the loop stops after the first hypothesis with more than
+    `early_exit` inliers, the best one is the first with the largest count.
+
+    Returns a Sim3Estimate of device tensors (R, t, s and sim3 in the input
+    dtype); status 1: no hypothesis had an inlier (the reference returns None,
+    here the model is the identity), 2: the refit was degenerate.  No host
+    sync when the samples are drawn here; given samples are range-checked,
+    which costs one host read (not while a graph is being captured).
+    """
+    drawn = samples is None
+    if drawn:
+        samples = draw_samples(src_points.shape[0], iterations, src_points.device, generator)
+    model, info, mask = cuda_ba.ransac_umeyama(src_points, dst_points, samples, float(threshold),
+                                               int(early_exit), check_samples=not drawn)
+    m = model.to(src_points.dtype)
+    return Sim3Estimate(m[:9].view(3, 3), m[9:12], m[12], m[13:21], info[0], mask, info[1],
+                        info[3], info)
+
+
+def close_loop(poses_, n, loop_ii, loop_jj, i, j, i_pts, j_pts, min_inliers=30, iterations=400,
+               threshold=0.1, samples=None, generator=None, pgo_iters=30):
+    """The loop closure of frames (i, j) from their matched 3-D points on
+    (long_term.py:235-266): estimate the Sim3 that maps i_pts onto j_pts, join
+    it with the relative poses of the earlier loops and optimise the pose graph.
+
+    poses_ [>= n, 7]: the world-to-camera SE3 poses of the map (not modified);
+    loop_ii / loop_jj [L] int64 device tensors: the loops closed so far;
+    i_pts / j_pts [N, 3] matched points in the two frames.  Returns None when
+    there are too few points or inliers, else (final [safe_i, 8] as `run_pgo`
+    returns it, loop_ii and loop_jj with (i, j) appended, the Sim3Estimate).
+    The first test is `i_pts.numel() < min_inliers`: the reference compares
+    numpy's .size, 3 N, with the inlier threshold, and that is kept.  One host
+    read (status and inlier count) decides whether the optimiser runs (given
+    samples are range-checked before, as in `ransac_umeyama`); the reference's
+    worker process and result queue are not reproduced.
+    """
+    if i_pts.numel() < min_inliers:
+        return None
+    est = ransac_umeyama(i_pts, j_pts, iterations=iterations, threshold=threshold,
+                         samples=samples, generator=generator)
+    num_inliers, _, _, status = est.info.tolist()
+    if status != 0 or num_inliers < min_inliers:
+        return None
+    poses_ = poses_.view(-1, 7)
+    Gij = SE3(poses_[loop_jj]) * SE3(poses_[loop_ii]).inv()
+    loop_poses = torch.cat([SE3_to_Sim3(Gij).data, est.sim3[None].to(poses_.dtype)], dim=0)
+    new = torch.tensor([i, j], device=loop_ii.device, dtype=loop_ii.dtype)
+    loop_ii = torch.cat([loop_ii, new[:1]])
+    loop_jj = torch.cat([loop_jj, new[1:]])
+    pred_poses = SE3(poses_[:n]).inv()
+    final = run_pgo(pred_poses, loop_poses, loop_ii, loop_jj, iters=pgo_iters)
+    return final, loop_ii, loop_jj, est
+
+
+def _delta_sources(pairs, live):
+    """Index into `live` (the timestamps of the n keyframes) of the source
+    keyframe of every delta record (t1, t0): t0, followed through the records
+    while it is itself a removed frame (long_term.py:182-186)."""
+    back = {int(t1): int(t0) for t1, t0 in pairs}
+    index = {int(t): k for k, t in enumerate(live)}
+    out = []
+    for t1, _ in pairs:
+        t = int(t1)
+        for _ in range(len(back) + 1):
+            if t not in back:
+                break
+            t = back[t]
+        if t not in index:
+            raise ValueError(f"apply_result: delta record {int(t1)} leads to frame {t}, "
+                             "which is not a keyframe")
+        out.append(index[t])
+    return out
+
+
+def apply_result(final, poses_, patches_, n, M, delta=None, tstamps=None):
+    """Write run_pgo's result into the map, in place (lc_callback and
+    _rescale_deltas, long_term.py:175-203): poses_[:safe_i] = SE3(res)^-1,
+    the inverse depths of the patches of those frames divided by the frame's
+    scale, the translation of every delta record scaled by the scale of its
+    source keyframe (1 for frames >= safe_i), then PatchGraph.normalize.
+
+    final [safe_i, 8]; poses_ [N, 7]; patches_ [N*M, 3, P, P] (or with a
+    leading 1); delta = (log [cap, 7], tstamps [cap, 2] (t1, t0), count) as
+    `DevicePatchGraph.keyframe` records it, tstamps [>= n] the keyframes'
+    timestamps.  The walk along the records runs on a host copy of the two
+    integer tables (one read; loop closures are rare), the scaling is one
+    indexed multiply on the device.  Returns normalize's scale.
+    """
+    inv7, s = split_result(final)
+    safe_i = s.shape[0]
+    P7 = poses_.view(-1, 7)
+    P = patches_.shape[-1]
+    K = patches_.view(-1, M, 3, P, P)
+    P7[:safe_i] = inv7.to(P7.dtype)
+    K[:safe_i, :, 2] /= s.view(safe_i, 1, 1, 1).to(K.dtype)
+    log = None
+    if delta is not None:
+        if tstamps is None:
+            raise ValueError("apply_result: the delta log needs tstamps")
+        log, pairs, count = delta
+        count = int(count)
+        if count > 0:
+            src = _delta_sources(pairs[:count].tolist(), tstamps[:n].tolist())
+            s1 = torch.ones(n, device=log.device, dtype=log.dtype)
+            s1[:safe_i] = s.to(log.dtype)
+            log[:count, :3] *= s1[torch.tensor(src, device=log.device)][:, None]
+    return global_ba.normalize(P7, patches_, n, M, delta=log)

@@ -201,6 +201,35 @@ int dpvo_pgo_factor(const float* J_Ginv_i, const float* J_Ginv_j, const int64_t*
 int dpvo_pgo_back(const int64_t* plan, const int64_t* hdr, const double* xB, double* ws,
                   void* stream);
 
+/* Loop-closure measurement: RANSAC over 3-point Umeyama models and the refit
+   on the winner's inliers (replaces the numba ransac_umeyama /
+   umeyama_alignment of dpvo/loop_closure/optim_utils.py:64-150, which run on
+   the CPU over points copied off the GPU).  src / dst [N, 3] matched points
+   (dtype DPVO_F32 or DPVO_F64; arithmetic is fp64 either way, long_term.py:233
+   casts to double), dst ~ s R src + t.  samples [H, 3] int32: the three point
+   indices of each hypothesis, in the order the reference's loop would draw
+   them (an index outside [0, N) makes its hypothesis degenerate; nothing is
+   read out of range).  Two launches:
+     score   one wave per hypothesis: counts[h] = #{ |c R x + t - y| <
+             threshold } under the sample's Umeyama model, -1 for a degenerate
+             sample (fewer than 2 singular values above 2.220446049250313e-16);
+     select  stop = first h with counts[h] > early_exit (else H - 1); winner =
+             lowest h <= stop with the largest positive count; inlier_mask [N]
+             of the winner; Umeyama refit on the inliers, reduced in a fixed
+             order (bit-identical from run to run).
+   model [21] fp64: R row-major (9), t (3), s (1), then the Sim3 data
+   (tx, ty, tz, qx, qy, qz, qw, s) with qw >= 0.  info [4]: number of inliers,
+   winning hypothesis (-1: none), stop index, status -- 0 ok; 1 no hypothesis
+   with a positive count (identity model, 0 inliers, the reference returns
+   None); 2 the refit is degenerate (identity model; inliers and mask kept).
+   The workspace holds counts[H] int32 at its start.  NULL pointers, N < 3,
+   H < 1 or threshold <= 0: DPVO_ERR_INVALID before any launch. */
+size_t dpvo_ransac_umeyama_workspace_bytes(int N, int H);
+int dpvo_ransac_umeyama(const void* src, const void* dst, int N, int dtype,
+                        const int32_t* samples, int H, double threshold, int early_exit,
+                        double* model, int32_t* info, uint8_t* inlier_mask, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* Largest number of free poses (t1 - t0) dpvo_ba_forward handles. */
 int dpvo_ba_max_free_poses(void);
 
