@@ -3,6 +3,8 @@
 // Group ids follow dispatch.h:24-45; this build implements SO3 (1), SE3 (3),
 // the groups on DPVO's hot path, and Sim3 (4), the group of the loop-closure
 // pose graph.  RxSO3 (2) is not built: nothing in DPVO uses it on its own.
+#include <climits>
+
 #include "ext_common.hpp"
 
 using namespace dpvo_ext;
@@ -17,25 +19,79 @@ static void check_group(int g) {
 static int K_of(int g) { return g == 1 ? 3 : g == 3 ? 6 : 7; }
 static int N_of(int g) { return K_of(g) + 1; }
 
-// lietorch.cpp:7 CHECK_CONTIGUOUS
-#define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
-
 static int lie_dtype(const torch::Tensor& t) {
   TORCH_CHECK(t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kFloat64,
               "lietorch_backends: float32 / float64 only (dispatch.h:41-42)");
   return dtype_code(t);
 }
 
-static torch::Tensor fwd(int g, int op, torch::Tensor X, torch::Tensor Y, int out_dim) {
-  check_group(g);
-  check_device(X, "X");
-  CHECK_CONTIGUOUS(X);
-  if (Y.defined()) {
-    CHECK_CONTIGUOUS(Y);
-    TORCH_CHECK(Y.scalar_type() == X.scalar_type(), "dtype mismatch");
+// per-op row widths: what the kernels of lie.hip read from X, Y and grad
+static int x_dim(int g, int op) { return op == OP_EXP ? K_of(g) : N_of(g); }
+static int y_dim(int g, int op) {
+  switch (op) {
+    case OP_MUL: return N_of(g);
+    case OP_ADJ: case OP_ADJT: case OP_JINV: return K_of(g);
+    case OP_ACT: return 3;
+    case OP_ACT4: return 4;
+    default: return 0;  // unary
   }
+}
+static int grad_dim(int g, int op) {
+  switch (op) {
+    case OP_EXP: case OP_INV: case OP_MUL: return N_of(g);
+    case OP_ACT: return 3;
+    case OP_ACT4: return 4;
+    default: return K_of(g);  // LOG, ADJ, ADJT
+  }
+}
+
+// every operand is [n, width] contiguous rows of X's dtype on X's device: the
+// kernels index n * width elements of each, so anything else is refused here
+static void check_rows(const torch::Tensor& t, const char* name, const torch::Tensor& X, int64_t n,
+                       int width) {
+  TORCH_CHECK(t.dim() == 2, "lietorch_backends: ", name, " must be 2-D [n, ", width, "], got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.size(1) == width, "lietorch_backends: ", name, " must have ", width,
+              " columns, got ", t.size(1));
+  TORCH_CHECK(t.size(0) == n, "lietorch_backends: ", name, " has ", t.size(0), " rows, X has ", n);
+  TORCH_CHECK(t.scalar_type() == X.scalar_type(), "lietorch_backends: ", name,
+              " dtype mismatch with X");
+  TORCH_CHECK(t.is_contiguous(), "lietorch_backends: ", name, " must be contiguous");
+}
+static void check_on_device(const torch::Tensor& t, const char* name, const torch::Tensor& X) {
+  check_device(t, name);
+  TORCH_CHECK(t.device() == X.device(), "lietorch_backends: ", name, " is not on X's device");
+}
+
+// shapes and dtypes of all operands first, then where they live; `grad` is
+// null for a forward op.  Returns n.
+static int check_operands(int g, int op, const torch::Tensor& X, const torch::Tensor& Y,
+                          const torch::Tensor* grad) {
+  check_group(g);
+  TORCH_CHECK(X.defined(), "lietorch_backends: X is undefined");
+  lie_dtype(X);
+  TORCH_CHECK(X.dim() == 2, "lietorch_backends: X must be 2-D [n, ", x_dim(g, op), "], got ",
+              X.dim(), "-D");
+  const int64_t n = X.size(0);
+  TORCH_CHECK(n <= INT_MAX, "lietorch_backends: too many rows");
+  check_rows(X, "X", X, n, x_dim(g, op));
+  const int yd = y_dim(g, op);
+  TORCH_CHECK(Y.defined() == (yd > 0), "lietorch_backends: op ", op,
+              yd > 0 ? " needs a second operand" : " takes one operand");
+  if (yd > 0) check_rows(Y, "Y", X, n, yd);
+  if (grad) {
+    TORCH_CHECK(grad->defined(), "lietorch_backends: grad is undefined");
+    check_rows(*grad, "grad", X, n, grad_dim(g, op));
+  }
+  check_on_device(X, "X", X);
+  if (yd > 0) check_on_device(Y, "Y", X);
+  if (grad) check_on_device(*grad, "grad", X);
+  return (int)n;
+}
+
+static torch::Tensor fwd(int g, int op, torch::Tensor X, torch::Tensor Y, int out_dim) {
+  const int n = check_operands(g, op, X, Y, nullptr);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
-  const int n = X.size(0);
   auto out = torch::empty({n, out_dim}, X.options());
   check_status(dpvo_lie_forward(g, op, lie_dtype(X), n, X.data_ptr(),
                                 Y.defined() ? Y.data_ptr() : nullptr, out.data_ptr(),
@@ -46,15 +102,10 @@ static torch::Tensor fwd(int g, int op, torch::Tensor X, torch::Tensor Y, int ou
 
 static std::vector<torch::Tensor> bwd(int g, int op, torch::Tensor grad, torch::Tensor X,
                                       torch::Tensor Y, int d0, int d1) {
-  check_group(g);
-  check_device(X, "X");
-  CHECK_CONTIGUOUS(X);
-  CHECK_CONTIGUOUS(grad);
-  if (Y.defined()) CHECK_CONTIGUOUS(Y);
+  const int n = check_operands(g, op, X, Y, &grad);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
-  const int n = X.size(0);
-  auto o0 = torch::empty({n, d0}, grad.options());
-  auto o1 = d1 > 0 ? torch::empty({n, d1}, grad.options()) : torch::Tensor();
+  auto o0 = torch::empty({n, d0}, X.options());
+  auto o1 = d1 > 0 ? torch::empty({n, d1}, X.options()) : torch::Tensor();
   check_status(dpvo_lie_backward(g, op, lie_dtype(X), n, grad.data_ptr(), X.data_ptr(),
                                  Y.defined() ? Y.data_ptr() : nullptr, o0.data_ptr(),
                                  d1 > 0 ? o1.data_ptr() : nullptr, current_stream()),

@@ -66,48 +66,86 @@ __device__ __forceinline__ void mm3(const S* A, const S* B, S* C) {
     for (int j = 0; j < 3; j++)
       C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
 }
-template <typename S>
-__device__ __forceinline__ S eps() { return S(1e-6); }  // common.h:7
+// ---- coefficient functions ----
+// Every scalar coefficient of Exp, Log, J_l, J_l^-1 and Q is a function of
+// t2 = theta^2 alone.  The textbook closed forms (so3.h:175-268, se3.h:133-162)
+// cancel for small theta -- (1 - cos t) / t^2 loses 1 / t^2 of the precision,
+// Q's (2t - 3 sin t + t cos t) / (2 t^5) loses 1 / t^4 -- and lietorch's switch
+// to a two-term series only below theta = 1e-6 leaves the whole band up to
+// ~1e-2 wrong: 1e-9 in fp64, 1e-2 in fp32.  Here they are evaluated in fp64
+// for both tensor types (a handful of scalar operations per element; the
+// matrix algebra around them stays in S), by five terms of the series in t2
+// below sim3::kTheta2 (next term < 1e-17 of the leading one) and above it by
+// forms whose cancellation costs at most 1 / t2 = 400 roundoffs of fp64.
+struct JlCoef {
+  double b, c;  // (1 - cos t) / t^2, (t - sin t) / t^3
+};
+__device__ __forceinline__ JlCoef jl_coef(double t2) {
+  JlCoef k;
+  if (t2 < sim3::kTheta2) {
+    k.b = 0.5 - t2 * (1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800))));
+    k.c = 1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880 - t2 * (1.0 / 39916800))));
+  } else {
+    const double t = sqrt(t2), sh = sin(0.5 * t);
+    k.b = 2 * sh * sh / t2;  // 1 - cos t = 2 sin^2(t / 2)
+    k.c = (t - sin(t)) / (t2 * t);
+  }
+  return k;
+}
+// (t^2 + 2 cos t - 2) / (2 t^4) and (2t - 3 sin t + t cos t) / (2 t^5) of se3_Q
+__device__ __forceinline__ void q_coef(double t2, const JlCoef& k, double& c2, double& c3) {
+  if (t2 < sim3::kTheta2) {
+    c2 = 1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800 - t2 * (1.0 / 479001600))));
+    c3 = 1.0 / 120 - t2 * (2.0 / 5040 - t2 * (3.0 / 362880 - t2 * (4.0 / 39916800 - t2 * (5.0 / 6227020800))));
+  } else {  // the same numerators through b and c
+    c2 = (0.5 - k.b) / t2;
+    c3 = (3 * k.c - k.b) / (2 * t2);
+  }
+}
+// (1 - (t / 2) cot(t / 2)) / t^2 of J_l^-1
+__device__ __forceinline__ double jl_inv_coef(double t2) {
+  if (t2 < sim3::kTheta2)
+    return 1.0 / 12 + t2 * (1.0 / 720 + t2 * (1.0 / 30240 + t2 * (1.0 / 1209600 + t2 * (1.0 / 47900160))));
+  const double ht = 0.5 * sqrt(t2);
+  return (1 - ht * cos(ht) / sin(ht)) / t2;
+}
 
 template <typename S>
 __device__ __forceinline__ void so3_log(const Q4<S>& q, S* o) {  // so3.h:175-211
-  const S sq = q.x * q.x + q.y * q.y + q.z * q.z;
-  const S w = q.w;
-  S f;
-  if (sq < eps<S>() * eps<S>()) {
-    f = S(2) / w - S(2.0 / 3.0) * sq / (w * w * w);
-  } else {
-    const S n = sqrt(sq);
-    if (fabs(w) < eps<S>())
-      f = (w > S(0) ? S(3.14159265358979323846) : -S(3.14159265358979323846)) / n;
-    else
-      f = S(2) * atan(n / w) / n;
+  const double sq = (double)q.x * q.x + (double)q.y * q.y + (double)q.z * q.z;
+  const double w = q.w;
+  double f;  // 2 atan(n / w) / n, n = |v|
+  if (sq < sim3::kLogR2 * w * w) {
+    const double r = sq / (w * w);
+    f = 2 / w * (1 - r * (1.0 / 3 - r * (1.0 / 5 - r * (1.0 / 7 - r * (1.0 / 9 - r * (1.0 / 11))))));
+  } else {  // atan2 is exact through w = 0 (theta = pi), where lietorch puts +-pi / n
+    const double n = sqrt(sq);
+    f = (w < 0 ? -2 : 2) * atan2(n, fabs(w)) / n;
   }
-  o[0] = f * q.x; o[1] = f * q.y; o[2] = f * q.z;
+  o[0] = (S)(f * q.x); o[1] = (S)(f * q.y); o[2] = (S)(f * q.z);
 }
 template <typename S>
 __device__ __forceinline__ Q4<S> so3_exp(const S* phi) {  // so3.h:213-230
-  const S t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
-  const S t = sqrt(t2);
-  S im, re;
-  if (t < eps<S>()) {
-    const S t4 = t2 * t2;
-    im = S(0.5) - S(1.0 / 48.0) * t2 + S(1.0 / 3840.0) * t4;
-    re = S(1) - S(1.0 / 8.0) * t2 + S(1.0 / 384.0) * t4;
+  const double t2 = (double)(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]);
+  double im, re;
+  if (t2 < sim3::kTheta2) {
+    const double h = 0.25 * t2;  // (theta / 2)^2
+    im = 0.5 * (1 - h * (1.0 / 6 - h * (1.0 / 120 - h * (1.0 / 5040 - h * (1.0 / 362880)))));
+    re = 1 - h * (0.5 - h * (1.0 / 24 - h * (1.0 / 720 - h * (1.0 / 40320))));
   } else {
-    im = sin(S(0.5) * t) / t;
-    re = cos(S(0.5) * t);
+    const double t = sqrt(t2);
+    im = sin(0.5 * t) / t;
+    re = cos(0.5 * t);
   }
-  return qnorm<S>(im * phi[0], im * phi[1], im * phi[2], re);
+  return qnorm<S>((S)im * phi[0], (S)im * phi[1], (S)im * phi[2], (S)re);
 }
 template <typename S>
 __device__ __forceinline__ void so3_jl(const S* phi, S* J) {  // so3.h:232-250
   S Ph[9], Ph2[9];
   hat(phi, Ph);
   mm3(Ph, Ph, Ph2);
-  const S t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], t = sqrt(t2);
-  const S c1 = (t < eps<S>()) ? S(0.5) - S(1.0 / 24.0) * t2 : (S(1) - cos(t)) / t2;
-  const S c2 = (t < eps<S>()) ? S(1.0 / 6.0) - S(1.0 / 120.0) * t2 : (t - sin(t)) / (t2 * t);
+  const JlCoef k = jl_coef((double)(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]));
+  const S c1 = (S)k.b, c2 = (S)k.c;
   for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0 ? S(1) : S(0)) + c1 * Ph[i] + c2 * Ph2[i];
 }
 template <typename S>
@@ -115,9 +153,7 @@ __device__ __forceinline__ void so3_jl_inv(const S* phi, S* J) {  // so3.h:252-2
   S Ph[9], Ph2[9];
   hat(phi, Ph);
   mm3(Ph, Ph, Ph2);
-  const S t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], t = sqrt(t2);
-  const S ht = S(0.5) * t;
-  const S c2 = (t < eps<S>()) ? S(1.0 / 12.0) : (S(1) - t * cos(ht) / (S(2) * sin(ht))) / (t * t);
+  const S c2 = (S)jl_inv_coef((double)(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]));
   for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0 ? S(1) : S(0)) + S(-0.5) * Ph[i] + c2 * Ph2[i];
 }
 template <typename S>
@@ -125,13 +161,11 @@ __device__ __forceinline__ void se3_Q(const S* xi, S* Qm) {  // se3.h:133-162
   S Ta[9], Ph[9];
   hat(xi, Ta);
   hat(xi + 3, Ph);
-  const S t = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-  const S t2 = t * t, t4 = t2 * t2;
-  const S c1 = (t < eps<S>()) ? S(1.0 / 6.0) - S(1.0 / 120.0) * t2 : (t - sin(t)) / (t2 * t);
-  const S c2 = (t < eps<S>()) ? S(1.0 / 24.0) - S(1.0 / 720.0) * t2
-                              : (t2 + 2 * cos(t) - 2) / (2 * t4);
-  const S c3 = (t < eps<S>()) ? S(1.0 / 120.0) - S(1.0 / 2520.0) * t2
-                              : (2 * t - 3 * sin(t) + t * cos(t)) / (2 * t4 * t);
+  const double t2 = (double)(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+  const JlCoef k = jl_coef(t2);
+  double d2, d3;
+  q_coef(t2, k, d2, d3);
+  const S c1 = (S)k.c, c2 = (S)d2, c3 = (S)d3;
   S PT[9], TP[9], PTP[9], PPT[9], TPP[9], PTPP[9], PPTP[9];
   mm3(Ph, Ta, PT); mm3(Ta, Ph, TP); mm3(PT, Ph, PTP);
   mm3(Ph, PT, PPT); mm3(TP, Ph, TPP); mm3(PTP, Ph, PTPP); mm3(Ph, PTP, PPTP);

@@ -60,7 +60,6 @@ DPVO_HD double f_sin(double x) { return ::sin(x); }
 DPVO_HD double f_cos(double x) { return ::cos(x); }
 DPVO_HD double f_exp(double x) { return ::exp(x); }
 DPVO_HD double f_log(double x) { return ::log(x); }
-DPVO_HD double f_atan(double x) { return ::atan(x); }
 DPVO_HD Dual f_sqrt(const Dual& x) {
   const double r = ::sqrt(x.v);
   return {r, x.d / (2.0 * r)};
@@ -72,8 +71,9 @@ DPVO_HD Dual f_exp(const Dual& x) {
   return {e, e * x.d};
 }
 DPVO_HD Dual f_log(const Dual& x) { return {::log(x.v), x.d / x.v}; }
-DPVO_HD Dual f_atan(const Dual& x) {
-  return {::atan(x.v), x.d / (1.0 + x.v * x.v)};
+DPVO_HD double f_atan2(double y, double x) { return ::atan2(y, x); }
+DPVO_HD Dual f_atan2(const Dual& y, const Dual& x) {
+  return {::atan2(y.v, x.v), (x.v * y.d - y.v * x.d) / (x.v * x.v + y.v * y.v)};
 }
 
 template <typename T>
@@ -236,11 +236,10 @@ DPVO_HD void logm(const Elem<T>& g, T* x) {  // sim3.h:145-154, rxso3.h:131-166
     f = T(2.0) / w *
         (T(1.0) - r * (T(1.0 / 3.0) - r * (T(1.0 / 5.0) - r * (T(1.0 / 7.0) - r * (T(1.0 / 9.0) - r * T(1.0 / 11.0))))));
   } else {
+    // 2 atan(n / w) / n by atan2: value and derivative stay right through
+    // w = 0 (theta = pi), where lietorch switches to the constant +-pi / n
     const T n = f_sqrt(sq);
-    if (fabs(val(w)) < 1e-6)
-      f = T(val(w) > 0.0 ? 3.14159265358979323846 : -3.14159265358979323846) / n;
-    else
-      f = T(2.0) * f_atan(n / w) / n;
+    f = val(w) < 0.0 ? -(T(2.0) * f_atan2(n, -w) / n) : T(2.0) * f_atan2(n, w) / n;
   }
   T* phi = x + 3;
   phi[0] = f * g.q[0]; phi[1] = f * g.q[1]; phi[2] = f * g.q[2];

@@ -678,8 +678,6 @@ static int ba_core(float* poses, float* patches, const float* intrinsics, const 
 /* Quaternions are (x,y,z,w) and normalised on load (so3.h:95-97).           */
 /* ------------------------------------------------------------------------ */
 
-#define EPS 1e-6 /* common.h:7 */
-#define PI_D 3.14159265358979323846
 
 typedef struct { double q[4]; } so3_t;           /* x y z w */
 typedef struct { double t[3]; so3_t r; } se3_t;
@@ -737,61 +735,84 @@ static void mm3(const double* A, const double* B, double* C) {
       C[i * 3 + j] = s;
     }
 }
+/* Coefficient functions of Exp, Log, J_l, J_l^-1 and Q.  The closed forms of
+   so3.h / se3.h cancel for small theta and lietorch's two-term series starts
+   only below 1e-6, which leaves errors up to 1e-8 for theta in 1e-6 .. 1e-2.
+   Five terms of the series in t2 = theta^2 below THETA2_SERIES, forms that
+   lose at most 1 / t2 above it. */
+#define THETA2_SERIES 2.5e-3
+#define LOG_R2_SERIES 1.0e-4
+static void jl_coef(double t2, double* b, double* c) { /* (1-cos t)/t^2, (t-sin t)/t^3 */
+  if (t2 < THETA2_SERIES) {
+    *b = 0.5 - t2 * (1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800))));
+    *c = 1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880 - t2 * (1.0 / 39916800))));
+  } else {
+    const double t = sqrt(t2), sh = sin(0.5 * t);
+    *b = 2 * sh * sh / t2;
+    *c = (t - sin(t)) / (t2 * t);
+  }
+}
 static void so3_log(so3_t a, double out[3]) { /* so3.h:175-211 */
   const double sq = a.q[0] * a.q[0] + a.q[1] * a.q[1] + a.q[2] * a.q[2];
   const double w = a.q[3];
-  double f;
-  if (sq < EPS * EPS) {
-    f = 2.0 / w - (2.0 / 3.0) * sq / (w * w * w);
-  } else {
+  double f; /* 2 atan(n / w) / n */
+  if (sq < LOG_R2_SERIES * w * w) {
+    const double r = sq / (w * w);
+    f = 2 / w * (1 - r * (1.0 / 3 - r * (1.0 / 5 - r * (1.0 / 7 - r * (1.0 / 9 - r * (1.0 / 11))))));
+  } else { /* atan2: exact through w = 0 (theta = pi) */
     const double n = sqrt(sq);
-    if (fabs(w) < EPS) f = (w > 0 ? PI_D : -PI_D) / n;
-    else f = 2.0 * atan(n / w) / n;
+    f = (w < 0 ? -2 : 2) * atan2(n, fabs(w)) / n;
   }
   for (int i = 0; i < 3; i++) out[i] = f * a.q[i];
 }
 static so3_t so3_exp(const double* phi) { /* so3.h:213-230 */
   const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
-  const double t = sqrt(t2);
   double im, re;
-  if (t < EPS) {
-    const double t4 = t2 * t2;
-    im = 0.5 - (1.0 / 48.0) * t2 + (1.0 / 3840.0) * t4;
-    re = 1.0 - (1.0 / 8.0) * t2 + (1.0 / 384.0) * t4;
+  if (t2 < THETA2_SERIES) {
+    const double h = 0.25 * t2;
+    im = 0.5 * (1 - h * (1.0 / 6 - h * (1.0 / 120 - h * (1.0 / 5040 - h * (1.0 / 362880)))));
+    re = 1 - h * (0.5 - h * (1.0 / 24 - h * (1.0 / 720 - h * (1.0 / 40320))));
   } else {
+    const double t = sqrt(t2);
     im = sin(0.5 * t) / t;
     re = cos(0.5 * t);
   }
   return so3_norm(im * phi[0], im * phi[1], im * phi[2], re);
 }
 static void so3_left_jac(const double* phi, double J[9]) { /* so3.h:232-250 */
-  double Ph[9], Ph2[9];
+  double Ph[9], Ph2[9], c1, c2;
   hat3(phi, Ph);
   mm3(Ph, Ph, Ph2);
-  const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], t = sqrt(t2);
-  const double c1 = (t < EPS) ? 0.5 - (1.0 / 24.0) * t2 : (1.0 - cos(t)) / t2;
-  const double c2 = (t < EPS) ? 1.0 / 6.0 - (1.0 / 120.0) * t2 : (t - sin(t)) / (t2 * t);
+  jl_coef(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], &c1, &c2);
   for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0 ? 1.0 : 0.0) + c1 * Ph[i] + c2 * Ph2[i];
 }
 static void so3_left_jac_inv(const double* phi, double J[9]) { /* so3.h:252-268 */
-  double Ph[9], Ph2[9];
+  double Ph[9], Ph2[9], c2;
   hat3(phi, Ph);
   mm3(Ph, Ph, Ph2);
-  const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], t = sqrt(t2);
-  const double ht = 0.5 * t;
-  const double c2 = (t < EPS) ? 1.0 / 12.0 : (1.0 - t * cos(ht) / (2.0 * sin(ht))) / (t * t);
+  const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+  if (t2 < THETA2_SERIES) { /* (1 - (t/2) cot(t/2)) / t^2 */
+    c2 = 1.0 / 12 + t2 * (1.0 / 720 + t2 * (1.0 / 30240 + t2 * (1.0 / 1209600 + t2 * (1.0 / 47900160))));
+  } else {
+    const double ht = 0.5 * sqrt(t2);
+    c2 = (1.0 - ht * cos(ht) / sin(ht)) / t2;
+  }
   for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0 ? 1.0 : 0.0) - 0.5 * Ph[i] + c2 * Ph2[i];
 }
 static void se3_calcQ(const double* xi, double Qm[9]) { /* se3.h:133-162 */
   double Ta[9], Ph[9];
   hat3(xi, Ta);
   hat3(xi + 3, Ph);
-  const double t = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-  const double t2 = t * t, t4 = t2 * t2;
-  const double c1 = (t < EPS) ? 1.0 / 6.0 - (1.0 / 120.0) * t2 : (t - sin(t)) / (t2 * t);
-  const double c2 = (t < EPS) ? 1.0 / 24.0 - (1.0 / 720.0) * t2 : (t2 + 2 * cos(t) - 2) / (2 * t4);
-  const double c3 = (t < EPS) ? 1.0 / 120.0 - (1.0 / 2520.0) * t2
-                              : (2 * t - 3 * sin(t) + t * cos(t)) / (2 * t4 * t);
+  const double t2 = xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5];
+  double b, c1, c2, c3;
+  jl_coef(t2, &b, &c1);
+  if (t2 < THETA2_SERIES) {
+    c2 = 1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800 - t2 * (1.0 / 479001600))));
+    c3 = 1.0 / 120 - t2 * (2.0 / 5040 - t2 * (3.0 / 362880 - t2 * (4.0 / 39916800 - t2 * (5.0 / 6227020800))));
+  } else { /* (t^2 + 2 cos t - 2) / (2 t^4), (2t - 3 sin t + t cos t) / (2 t^5) through b, c1 */
+    c2 = (0.5 - b) / t2;
+    c3 = (3 * c1 - b) / (2 * t2);
+  }
   double PT[9], TP[9], PTP[9], PPT[9], TPP[9], PTPP[9], PPTP[9];
   mm3(Ph, Ta, PT); mm3(Ta, Ph, TP); mm3(PT, Ph, PTP);
   mm3(Ph, PT, PPT); mm3(TP, Ph, TPP); mm3(PTP, Ph, PTPP); mm3(Ph, PTP, PPTP);
