@@ -8,12 +8,14 @@ runs as DPVO's local call does: t0 = n - OPTIMIZATION_WINDOW (10), t1 = n
 (dpvo.py:818-824), so edges into the 12 fixed poses take part.
 Tolerances: north_star's 1e-4 relative bar on the pose delta, the
 inverse-depth delta and the last iteration's pose step dX
-(conftest.assert_ba_rel), plus poses 2e-5 abs, inverse depths 1e-4 rel."""
+(conftest.assert_ba_rel), the same bar on every free pose's step on its own
+(ba_gates.assert_per_pose), plus poses 2e-5 abs, inverse depths 1e-4 rel."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
+from ba_gates import assert_per_pose
 from conftest import assert_ba_rel
 from dpvo_amd import synthetic
 
@@ -52,6 +54,7 @@ def test_dpvo_window_matches_oracle(cb, gpu, M, iters):
     P, K = P.cpu().numpy(), K.cpu().numpy()
     assert_ba_rel(P, K, Pr, Kr, G.poses.numpy(), G.patches.numpy(), t0, t1, dX.cpu().numpy(),
                   d["dX"])
+    assert_per_pose(dX.cpu().numpy(), d["dX"])  # no pose hides in the norm-wise bar
     np.testing.assert_allclose(P, Pr, rtol=0, atol=2e-5)
     np.testing.assert_allclose(K[:, 2], Kr[:, 2], rtol=1e-4, atol=1e-5)
     np.testing.assert_array_equal(P[:t0], G.poses.numpy()[:t0])  # fixed poses untouched
@@ -107,6 +110,7 @@ def test_bench_call_matches_oracle_rel(cb, gpu, iters, features):
     e = assert_ba_rel(poses.cpu().numpy(), patches.cpu().numpy(), Pr, Kr, G.poses.numpy(),
                       G.patches.numpy(), t0, t1, dX, d["dX"])
     assert e["dP"] < 1e-5  # measured: 0 (1 iteration) / 4.2e-6 (2 iterations)
+    assert_per_pose(dX, d["dX"])  # no pose hides in the norm-wise bar
 
 
 @pytest.mark.parametrize("cfg", ["cfg1", "cfg2"])
