@@ -415,7 +415,7 @@ __global__ void reproject_kernel(const float* __restrict__ poses, const float* _
                                  int num_patches, float* __restrict__ coords,
                                  int* __restrict__ order, int N2) {
   if (order && blockIdx.x == gridDim.x - 1) {  // extra workgroup: A-CORR edge order
-    __shared__ int bins[kOrderBins + 1];
+    __shared__ int bins[kOrderLds];
     const OrderIn q{poses, patches, intrinsics, ii, kk, P, num_poses, num_patches};
     edge_order_block(q, jj, E, N2, order, bins);
     return;

@@ -29,8 +29,7 @@ __device__ inline int fscan(int* data, int n, int* scr, int pack_shift = 0) {
   const int tid = threadIdx.x, nt = blockDim.x;
   if (n <= 0) {
     // keep the barrier of every other path: callers rely on it to order their
-    // LDS atomics before reading the results (plan_sharded's ctl[4..6] on a
-    // shard with an empty kk range)
+    // LDS atomics before reading the results
     __syncthreads();
     return 0;
   }

@@ -505,14 +505,13 @@ __device__ __forceinline__ void plan_block(const int64_t* __restrict__ ii,
 // ---- the plan over S workgroups (shard s of S) ----
 // Every shard makes the pass over the whole edge list (kk / ii / jj of 10k
 // edges = 240 KB, L2-resident after the first shard), so kmin / kmax / fmin /
-// status and the presence bitmap of patch ids are known everywhere; shard s
-// then groups only the edges of ITS bucket range [lo, hi) of kk - kmin:
-//   positions  = edges with a smaller kk (counted in the pass) + the local
-//                counting sort,
-//   patch ids  = present kk values below lo (bitmap popcount) + local index.
+// status and the histogram of kk are known everywhere, and every shard scans
+// that whole histogram: first positions and patch indices of all buckets are
+// global in every shard.  Shard s then groups only the edges of ITS bucket
+// range [lo, hi) of kk - kmin (scatter, block work, rank, stores).
 // The shards write disjoint ranges of epos / poff / pkk / pmask: no exchange
 // between workgroups.  Falls back to plan_block in shard 0 when the kk range
-// or the LDS does not fit.
+// does not fit the histogram's ring.
 __host__ __device__ constexpr int plan_shards(int E) {
   return E <= 512 ? 1 : ((E + 511) / 512 < kPlanShardMax ? (E + 511) / 512 : kPlanShardMax);
 }
@@ -538,21 +537,94 @@ __device__ __forceinline__ void plan_sharded_k(const int64_t* __restrict__ ii,
     }
   };
   stamp(0);
-  //   [ctl 256 B | code u16[cap] | spos u16[cap] | hf int[R] | pm u32[nl]]
-  const int tid = threadIdx.x, lane = tid & 63, T = kPT;
-  int* ctl = (int*)lds;  // [0..3] as plan_edges_pass, [4] below, [5] ubelow, [6] nuniq
-  int* scr = ctl + 16;
-  unsigned short* code = (unsigned short*)(lds + 256);
-  unsigned short* spos = code + cap;
-  int* hf = reinterpret_cast<int*>(spos + cap);  // histogram of kk - kmin over the FULL range
+  //   [ctl 256 B | spos u16[cap] | sv u16[cap] | wl int[kWMaxNB] | hf int[Z] | pm u32[pmN]]
+  // hf is a histogram of kk over a power-of-two ring of Z slots (slot = kk &
+  // (Z - 1)): it needs no kmin, so it is counted in the pass over the edges
+  // (one barrier for kmin / kmax / fmin and the histogram); a kk range wider
+  // than Z falls back to plan_block.
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, T = kPT;
+  int* ctl = (int*)lds;  // [0..3] kmin, kmax, fmin, status; [4] / [5] first position of bucket lo / hi
+  int* scr = ctl + 16;   // [kPT / 64] wave totals of the scan
+  unsigned short* spos = (unsigned short*)(lds + 256);  // edge at position p
+  unsigned short* sv = spos + cap;                      // its bucket - lo
+  int* wl = reinterpret_cast<int*>(sv + cap);           // [kWMaxNB] block work of this shard's patches
+  int* hf = wl + kWMaxNB;
+  const int avail = (int)((lds_bytes - 256 - 4 * (size_t)cap) / 4) - kWMaxNB;
+  int Z = 16384;
+  while (Z > 64 && Z + ((Z / S + 8) & ~3) > avail) Z >>= 1;
+  const int zm = Z - 1, pmN = (Z / S + 8) & ~3;
+  unsigned* pm = reinterpret_cast<unsigned*>(hf + Z);   // [nl] free-pose mask of bucket lo + v
+  const int kmaxc = num_patches - 1;
+  // ---- the edge list: every load of a round issued, then (first round) the
+  // zeroing and its barrier inside the loads' latency ----
+  constexpr int kRound = kPer % 5 == 0 ? 5 : kPer;
+  static_assert(kPer % kRound == 0, "load rounds");
   int kv[kPer];
-  plan_edges_pass<kPer>(ii, jj, kk, E, num_patches, num_poses, t0, N, ctl, code, kv);
-  stamp(1);
-  const int kmin = ctl[0], R = ctl[1] - kmin + 1;
-  const int nlmax = (R + S - 1) / S;
-  const bool fits = E > 0 && R <= kHistMax && E < (1 << 14) &&
-                    256 + 4 * (size_t)cap + 4 * (size_t)R + 4 * (size_t)nlmax + 4 * kWMaxNB <= lds_bytes;
-  if (!fits) {  // shard-uniform (every shard saw the same edges)
+  unsigned mk[kPer];  // free-pose bits of the edge
+  int kmin = 0x7fffffff, kmax = -1, fmin = 0x7fffffff, bad = 0;
+#pragma unroll
+  for (int r = 0; r < kPer; r++) {
+    kv[r] = 0;
+    mk[r] = 0u;
+  }
+#pragma unroll
+  for (int r0 = 0; r0 < kPer; r0 += kRound) {
+    if (r0 > 0 && r0 * T >= E) break;  // block-uniform: only the rounds that hold edges
+    int64_t vk[kRound], vi[kRound], vj[kRound];
+#pragma unroll
+    for (int r = 0; r < kRound; r++) {
+      const int e = min(tid + (r0 + r) * T, E - 1);
+      vk[r] = kk[e];
+      vi[r] = ii[e];
+      vj[r] = jj[e];
+    }
+    if (r0 == 0) {
+      int4* z = reinterpret_cast<int4*>(wl);
+      for (int q = tid; q < (kWMaxNB + Z + pmN) / 4; q += T) z[q] = make_int4(0, 0, 0, 0);
+      if (tid == 0) {
+        ctl[0] = 0x7fffffff;
+        ctl[1] = -1;
+        ctl[2] = 0x7fffffff;
+        ctl[3] = 0;
+      }
+      lds_barrier();
+      stamp(1);
+    }
+#pragma unroll
+    for (int r = 0; r < kRound; r++) {
+      const int e = tid + (r0 + r) * T;
+      if (e >= E) continue;
+      int64_t v = vk[r];
+      if (v < 0 || v > kmaxc) {
+        bad = 1;
+        v = v < 0 ? 0 : kmaxc;
+      }
+      kmin = min(kmin, (int)v);
+      kmax = max(kmax, (int)v);
+      kv[r0 + r] = (int)v;
+      atomicAdd(&hf[(int)v & zm], 1);
+      const int64_t gi = vi[r], gj = vj[r];
+      const bool fi = gi >= t0 && gi < t0 + N, fj = gj >= t0 && gj < t0 + N;
+      if (!fi) fmin = min(fmin, (int)min(max(gi, (int64_t)0), (int64_t)num_poses - 1));
+      if (!fj) fmin = min(fmin, (int)min(max(gj, (int64_t)0), (int64_t)num_poses - 1));
+      mk[r0 + r] = (fi ? 1u << (int)(gi - t0) : 0u) | (fj ? 1u << (int)(gj - t0) : 0u);
+    }
+  }
+  kmin = wave_min_i(kmin);
+  kmax = wave_max_i(kmax);
+  fmin = wave_min_i(fmin);
+  bad = wave_max_i(bad);
+  if (lane == 0) {
+    atomicMin(&ctl[0], kmin);
+    atomicMax(&ctl[1], kmax);
+    atomicMin(&ctl[2], fmin);
+    if (bad) atomicOr(&ctl[3], kStClamp);
+  }
+  lds_barrier();  // histogram, kmin / kmax / fmin / status complete
+  stamp(2);
+  kmin = ctl[0];
+  const int R = ctl[1] - kmin + 1;
+  if (__builtin_expect(R > Z || E >= (1 << 14), 0)) {  // shard-uniform (every shard saw the same edges)
     if (s == 0) {
       __syncthreads();  // ctl is re-initialised by plan_block
       plan_block(ii, jj, kk, E, num_patches, num_poses, t0, N, plan, lds, cap);
@@ -560,89 +632,83 @@ __device__ __forceinline__ void plan_sharded_k(const int64_t* __restrict__ ii,
     return;
   }
   const int lo = (int)((long long)R * s / S), hi = (int)((long long)R * (s + 1) / S), nl = hi - lo;
-  unsigned* pm = reinterpret_cast<unsigned*>(hf + R);
-  int* wl = reinterpret_cast<int*>(pm + nl);  // [kWMaxNB] block work of this shard's patches
-  for (int v = tid; v < R; v += T) hf[v] = 0;
-  for (int v = tid; v < nl; v += T) pm[v] = 0u;
-  for (int v = tid; v < kWMaxNB; v += T) wl[v] = 0;
-  if (tid == 0) {
-    ctl[4] = 0;
-    ctl[5] = 0;
-    ctl[6] = 0;
-  }
-  __syncthreads();
-  // one histogram of the whole kk range: its nonzero buckets below lo number
-  // the patches before this shard's, and its [lo, hi) slice is the local
-  // counting sort's input (a patch's ~4-10 edges share a bucket; a presence
-  // bitmap word took 32 patches' worth of atomics)
-  int nb = 0;
+  // ---- one packed exclusive scan of the whole range by all waves (bucket v:
+  // first position << 14 | patch index; plan_block's fast path), each thread a
+  // run of per buckets.  Every shard scans everything, so positions and patch
+  // indices are global and nothing has to be counted below lo; only the
+  // shard's own buckets are written back. ----
+  const int per = (R + T - 1) / T, v0 = tid * per, v1 = min(v0 + per, R);
+  int sum = 0;
+  for (int k0 = v0; k0 < v1; k0 += 4) {
+    int c[4];
 #pragma unroll
-  for (int r = 0; r < kPer; r++) {
-    const int e = tid + r * T;
-    if (e >= E) continue;
-    const int v = kv[r] - kmin;
-    atomicAdd(&hf[v], 1);
-    nb += v < lo ? 1 : 0;
-  }
-  __syncthreads();  // histogram complete
-  stamp(2);
-  int ub = 0, nu = 0;
-  for (int v = tid; v < R; v += T) {
-    const int present = hf[v] > 0 ? 1 : 0;
-    nu += present;
-    ub += v < lo ? present : 0;
-  }
-  nb = wave_sum_i(nb);
-  ub = wave_sum_i(ub);
-  nu = wave_sum_i(nu);
-  if (lane == 0) {
-    atomicAdd(&ctl[4], nb);
-    atomicAdd(&ctl[5], ub);
-    atomicAdd(&ctl[6], nu);
-  }
-  int* hist = hf + lo;  // this shard's buckets
-  // local counting sort in one packed scan (plan_block's fast path); the
-  // scan's barriers also complete the ctl sums above
-  fscan(hist, nl, scr, 14);
-  stamp(3);
-  const int below = ctl[4], ubelow = ctl[5], nuniq = ctl[6];
+    for (int j = 0; j < 4; j++) c[j] = hf[(kmin + min(k0 + j, v1 - 1)) & zm];
 #pragma unroll
-  for (int r = 0; r < kPer; r++) {
-    const int e = tid + r * T;
-    const int v = kv[r] - kmin - lo;
-    if (e >= E || v < 0 || v >= nl) continue;
-    const int old = atomicAdd(&hist[v], 1 << 14);
-    spos[old >> 14] = (unsigned short)e;
-    const unsigned c = code[e], ci = c & 0xff, cj = c >> 8;
-    const unsigned m = (ci != kFix ? 1u << ci : 0u) | (cj != kFix ? 1u << cj : 0u);
-    if (m) atomicOr(&pm[old & 0x3fff], m);
+    for (int j = 0; j < 4; j++) sum += k0 + j < v1 ? (c[j] << 14) | (c[j] > 0 ? 1 : 0) : 0;
   }
-  __syncthreads();
-  stamp(4);
-  // block work of the local patches (bucket v: edges end(v) - end(v - 1))
-  plan_block_work(nl, [&](int v, int& c, unsigned& m) {
-    const int hv = hist[v];
-    c = (hv >> 14) - (v == 0 ? 0 : (hist[v - 1] >> 14));
-    m = pm[hv & 0x3fff];
-  }, wl);
-  stamp(5);
+  const int incl = wave_incl_sum(sum);
+  if (lane == 63) scr[wid] = incl;
+  lds_barrier();
+  int total = 0, run = incl - sum;
 #pragma unroll
-  for (int r = 0; r < kPer; r++) {
-    const int e = tid + r * T;
-    const int v = kv[r] - kmin - lo;
-    if (e >= E || v < 0 || v >= nl) continue;
-    const int hv = hist[v];
-    const int b = hv >> 14, a = (v == 0) ? 0 : (hist[v - 1] >> 14);
-    const int rank = bucket_rank(spos, a, b, e);
-    plan.epos[below + a + rank] = e;
-    if (rank == 0) {
-      const int u = ubelow + (hv & 0x3fff);
-      plan.poff[u] = below + a;
-      plan.pkk[u] = kv[r];
-      plan.pmask[u] = pm[hv & 0x3fff];
+  for (int w = 0; w < kPT / 64; w++) {
+    const int x = scr[w];
+    total += x;
+    run += w < wid ? x : 0;
+  }
+  for (int k0 = v0; k0 < v1; k0 += 4) {
+    int c[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) c[j] = hf[(kmin + min(k0 + j, v1 - 1)) & zm];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int v = k0 + j;
+      if (v >= v1) continue;
+      if (v >= lo && v < hi) hf[(kmin + v) & zm] = run;
+      if (v == lo) ctl[4] = run >> 14;
+      if (v == hi) ctl[5] = run >> 14;
+      run += (c[j] << 14) | (c[j] > 0 ? 1 : 0);
     }
   }
-  __syncthreads();  // block work complete (the rank loop above does not touch wl)
+  lds_barrier();
+  stamp(3);
+  const int nuniq = total & 0x3fff;
+  const int below = ctl[4], top = hi < R ? ctl[5] : total >> 14;  // this shard's positions
+#pragma unroll
+  for (int r = 0; r < kPer; r++) {
+    const int e = tid + r * T;
+    const int v = kv[r] - kmin - lo;
+    if (e >= E || v < 0 || v >= nl) continue;
+    const int p = atomicAdd(&hf[kv[r] & zm], 1 << 14) >> 14;
+    spos[p] = (unsigned short)e;
+    sv[p] = (unsigned short)v;
+    if (mk[r]) atomicOr(&pm[v], mk[r]);
+  }
+  lds_barrier();
+  stamp(4);
+  // hf[bucket] >> 14 is now the END of the bucket; the patch index is unchanged.
+  // block work of the local patches
+  plan_block_work(nl, [&](int v, int& c, unsigned& m) {
+    c = (hf[(kmin + lo + v) & zm] >> 14) - (v == 0 ? below : (hf[(kmin + lo + v - 1) & zm] >> 14));
+    m = pm[v];
+  }, wl);
+  stamp(5);
+  // order inside a patch: one thread per POSITION of the shard (dense, about
+  // E / S of them) ranks its edge among the bucket's members
+  for (int p = below + tid; p < top; p += T) {
+    const int e = spos[p], v = sv[p];
+    const int hv = hf[(kmin + lo + v) & zm];
+    const int b = hv >> 14, a = v == 0 ? below : (hf[(kmin + lo + v - 1) & zm] >> 14);
+    const int rank = bucket_rank(spos, a, b, e);
+    plan.epos[a + rank] = e;
+    if (rank == 0) {
+      const int u = hv & 0x3fff;
+      plan.poff[u] = a;
+      plan.pkk[u] = kmin + lo + v;
+      plan.pmask[u] = pm[v];
+    }
+  }
+  lds_barrier();  // block work complete (the rank loop above does not touch wl)
   plan_store_work(plan, wl, s, N);
   if (tid == 0 && s == S - 1) plan.poff[nuniq] = E;
   if (tid == 0 && s == 0) {
@@ -658,18 +724,30 @@ __device__ __forceinline__ void plan_sharded_k(const int64_t* __restrict__ ii,
 
 // The executed code of the plan is what a cold instruction cache pays for
 // (the launch follows A-CORR and the BA window, which evict it): graphs of up
-// to 4 edges per thread (E <= 2048, cfg2) run a copy unrolled 4 deep instead
-// of kPlanPer = 20.
+// to 4 edges per thread (E <= 2048, cfg2) run a copy unrolled 4 deep.  The
+// copy unrolled kPlanPer = 20 deep and the plan_block fallback sit behind
+// branches marked unlikely, so block placement keeps them out of that copy's
+// straight line.  (As functions of their own -- noinline -- the kernel is 35
+// KB instead of 222 KB, but the call ABI costs it 227 VGPRs instead of 121 and
+// 156 B of scratch per lane: launch span 10.5 us instead of 10.1,
+// profiles/start_launch_chains/variants.txt.)
+__device__ __forceinline__ void plan_sharded_long(const int64_t* __restrict__ ii,
+                                               const int64_t* __restrict__ jj,
+                                               const int64_t* __restrict__ kk, int E, int num_patches,
+                                               int num_poses, int t0, int N, const Plan& plan,
+                                               char* lds, int cap, size_t lds_bytes, int s, int S) {
+  plan_sharded_k<kPlanPer>(ii, jj, kk, E, num_patches, num_poses, t0, N, plan, lds, cap, lds_bytes,
+                           s, S);
+}
 __device__ __forceinline__ void plan_sharded(const int64_t* __restrict__ ii,
                                              const int64_t* __restrict__ jj,
                                              const int64_t* __restrict__ kk, int E, int num_patches,
                                              int num_poses, int t0, int N, const Plan& plan,
                                              char* lds, int cap, size_t lds_bytes, int s, int S) {
-  if (E <= 4 * kPT)
+  if (__builtin_expect(E <= 4 * kPT, 1))
     plan_sharded_k<4>(ii, jj, kk, E, num_patches, num_poses, t0, N, plan, lds, cap, lds_bytes, s, S);
   else
-    plan_sharded_k<kPlanPer>(ii, jj, kk, E, num_patches, num_poses, t0, N, plan, lds, cap,
-                             lds_bytes, s, S);
+    plan_sharded_long(ii, jj, kk, E, num_patches, num_poses, t0, N, plan, lds, cap, lds_bytes, s, S);
 }
 
 __global__ void __launch_bounds__(kPT) ba_plan_kernel(const int64_t* __restrict__ ii,
@@ -685,8 +763,8 @@ __global__ void __launch_bounds__(kPT) ba_plan_kernel(const int64_t* __restrict_
 // One launch for the start of a DPVO update (dpvo.py:775-824): F-REPROJ of
 // every (edge, pixel), the A-CORR edge order and the BA plan.  The plan only
 // reads ii / jj / kk, which the update does not change before its BA, so its
-// single workgroup (the longest, dispatched first as workgroup 0) runs beside
-// the reprojection instead of after A-CORR.
+// workgroups (the longest, on the blocks that start first: launch_chain) run
+// beside the reprojection instead of after A-CORR.
 struct RArgs {
   const float* poses;
   const float* patches;
@@ -697,24 +775,45 @@ struct RArgs {
   int E, P, num_poses, num_patches, N2, t0, N;
   float* coords;
   int* order;
-  int nps;  // plan shards: workgroups [0, nps) plan, nps the edge order, then the reprojection
+  int nps;  // plan shards: chains [0, nps) plan, chain nps the edge order; the rest reprojects
+  int spread;  // chains on the blocks of XCDs 0 and 1 (launch_chain), else on blocks [0, nps]
   int64_t* marks;  // instrumentation (dpvo_ba_set_marks): [2b] / [2b + 1] start / end of workgroup b < 256
 };
 
+// Which block runs what.  Blocks go round the 8 XCDs by index, and inside the
+// update step the XCDs do not start a launch together: blocks of XCDs 0 and 1
+// start 1.7-2.8 us before those of XCDs 2-7 (scripts/launch_trace.py, stable
+// over steps and sessions).  The launch's long chains -- the nps plan shards,
+// then the edge order -- therefore take the blocks of XCDs 0 and 1: chain c
+// runs on block 8 (c / 2) + c % 2 (`spread`; the host sets it when the grid
+// holds those blocks).  The other blocks keep their order: rest(b) numbers
+// them 0, 1, ...
+__device__ __forceinline__ int launch_chain(const RArgs& R, int b) {  // chain of block b or -1
+  if (!R.spread) return b <= R.nps ? b : -1;
+  const int c = 2 * (b >> 3) + (b & 7);
+  return ((b & 7) < 2 && c <= R.nps) ? c : -1;
+}
+__device__ __forceinline__ int launch_rest(const RArgs& R, int b) {
+  if (!R.spread) return b - R.nps - 1;
+  return b - min(R.nps + 1, 2 * (b >> 3) + min(b & 7, 2));
+}
+inline int launch_spread(int nps, int grid) { return grid >= 8 * (nps / 2) + 2 ? 1 : 0; }
+
 __global__ void __launch_bounds__(kPT) reproject_plan_kernel(RArgs R, Plan plan) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  if ((int)blockIdx.x < R.nps) {
+  const int chain = launch_chain(R, blockIdx.x);
+  if (chain >= 0 && chain < R.nps) {
     plan_sharded(R.ii, R.jj, R.kk, R.E, R.num_patches, R.num_poses, R.t0, R.N, plan, lds, kWMaxE,
-                 kWLds, blockIdx.x, R.nps);
+                 kWLds, chain, R.nps);
     return;
   }
-  if ((int)blockIdx.x == R.nps) {
+  if (chain == R.nps) {
     const OrderIn q{R.poses, R.patches, R.intrinsics, R.ii, R.kk, R.P, R.num_poses, R.num_patches};
     edge_order_block(q, R.jj, R.E, R.N2, R.order, reinterpret_cast<int*>(lds));
     return;
   }
   const int PP = R.P * R.P;
-  const int t = (blockIdx.x - R.nps - 1) * kPT + threadIdx.x;
+  const int t = launch_rest(R, blockIdx.x) * kPT + threadIdx.x;
   if (t >= R.E * PP) return;
   reproject_pixel(R.poses, R.patches, R.intrinsics, R.ii, R.jj, R.kk, t / PP, t % PP, R.P,
                   R.num_poses, R.num_patches, R.coords);
@@ -735,30 +834,31 @@ struct InsArgs {
 template <typename T>
 __device__ __forceinline__ void reproject_plan_insert_body(const RArgs& R, const Plan& plan,
                                                            const InsArgs& I, int nrep, char* lds) {
-  const int b = blockIdx.x, b0 = R.nps + 1;  // first reprojection workgroup
+  const int chain = launch_chain(R, blockIdx.x);
   // the plan shards and the edge order are the launch's long chains; the
   // insertion tiles share their CUs: their waves issue first
-  if (b <= R.nps) __builtin_amdgcn_s_setprio(3);
-  if (b < R.nps) {
+  if (chain >= 0) __builtin_amdgcn_s_setprio(3);
+  if (chain >= 0 && chain < R.nps) {
     plan_sharded(R.ii, R.jj, R.kk, R.E, R.num_patches, R.num_poses, R.t0, R.N, plan, lds,
-                 plan_cap(R.E), plan_lds_bytes(plan_cap(R.E)), b, R.nps);
+                 plan_cap(R.E), plan_lds_bytes(plan_cap(R.E)), chain, R.nps);
     return;
   }
-  if (b == R.nps) {
+  if (chain == R.nps) {
     const OrderIn q{R.poses, R.patches, R.intrinsics, R.ii, R.kk, R.P, R.num_poses, R.num_patches};
     edge_order_block(q, R.jj, R.E, R.N2, R.order, reinterpret_cast<int*>(lds));
     return;
   }
-  if (b < b0 + nrep) {
+  const int b = launch_rest(R, blockIdx.x);  // reprojection blocks, then insertion tiles
+  if (b < nrep) {
     const int PP = R.P * R.P;
-    const int t = (b - b0) * kPT + threadIdx.x;
+    const int t = b * kPT + threadIdx.x;
     if (t >= R.E * PP) return;
     reproject_pixel(R.poses, R.patches, R.intrinsics, R.ii, R.jj, R.kk, t / PP, t % PP, R.P,
                     R.num_poses, R.num_patches, R.coords);
     return;
   }
   static_assert(kPT == 512, "two 256-thread insertion tiles per workgroup");
-  const int half = threadIdx.x >> 8, t = 2 * (b - b0 - nrep) + half;
+  const int half = threadIdx.x >> 8, t = 2 * (b - nrep) + half;
   const bool act = t < I.ntile;
   const int tt = act ? t : 0;
   float* tile = reinterpret_cast<float*>(lds) + half * kInsTC * kInsCS;
@@ -767,7 +867,7 @@ __device__ __forceinline__ void reproject_plan_insert_body(const RArgs& R, const
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kPT) reproject_plan_insert_kernel(RArgs R, Plan plan, InsArgs I,
+__global__ void __launch_bounds__(kPT, 2) reproject_plan_insert_kernel(RArgs R, Plan plan, InsArgs I,
                                                                     int nrep) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const bool mk = R.marks && blockIdx.x < 256;
@@ -2115,9 +2215,10 @@ int ba_window_reproject_plan(const float* poses, const float* patches, const flo
   r.coords = coords;
   r.order = order;
   r.nps = plan_shards(E);
-  const int total = E * P * P;
-  hipLaunchKernelGGL(reproject_plan_kernel, dim3(r.nps + 1 + (total + kPT - 1) / kPT), dim3(kPT), kWLds,
-                     as_stream(stream), r, plan);
+  const int total = E * P * P, grid = r.nps + 1 + (total + kPT - 1) / kPT;
+  r.spread = launch_spread(r.nps, grid);
+  hipLaunchKernelGGL(reproject_plan_kernel, dim3(grid), dim3(kPT), kWLds, as_stream(stream), r,
+                     plan);
   return launch_status();
 }
 
@@ -2167,11 +2268,12 @@ int ba_window_reproject_plan_insert(const float* poses, const float* patches,
   I.ntile = I.gx * I.gy * ((C + kInsTC - 1) / kInsTC);
   const int nrep = (E * P * P + kPT - 1) / kPT;
   const dim3 grid(r.nps + 1 + nrep + (I.ntile + 1) / 2);
+  r.spread = launch_spread(r.nps, (int)grid.x);
   // LDS sized for this E (the plan's need), not the kWMaxE maximum: the
   // insertion tiles then run several workgroups per CU beside the plan
   size_t lds = plan_lds_bytes(plan_cap(E));
   lds = std::max(lds, sizeof(float) * 2 * kInsTC * kInsCS);
-  lds = std::max(lds, sizeof(int) * (size_t)(kOrderBins + 2));
+  lds = std::max(lds, sizeof(int) * (size_t)kOrderLds);
   if (half)
     hipLaunchKernelGGL(reproject_plan_insert_kernel<__half>, grid, dim3(kPT), lds,
                        as_stream(stream), r, plan, I, nrep);

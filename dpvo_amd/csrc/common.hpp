@@ -62,6 +62,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// Workgroup barrier that orders LDS traffic only (same reasoning one level
+// up): global loads issued before it stay in flight across it.
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // wave64 inclusive scan of ints with DPP (row shifts 1/2/4/8 inside each row
 // of 16 lanes, then row_bcast:15 / row_bcast:31 across rows): six VALU ops
 // with a DPP source.  A __shfl_* is a ds_bpermute, an LDS round trip per
@@ -275,7 +283,7 @@ __device__ __forceinline__ void reproject_pixel(const float* __restrict__ poses,
 // near each other in the sequence, so the waves that share box lines run at
 // the same time (cfg2 fp32: 41.3 -> 40.4 us, scripts/corr_order_probe.py).
 // The centre is recomputed in both passes (no per-edge LDS: E is unbounded
-// here).  bins: >= kOrderBins + 1 ints of LDS.  Frames outside
+// here).  bins: kOrderLds ints of LDS.  Frames outside
 // [0, min(N2, kOrderBins / kOrderBands)) share the last frame's bins.
 struct OrderIn {
   const float* poses;
@@ -297,63 +305,64 @@ __device__ __forceinline__ int edge_order_key(const OrderIn& q, const int64_t* _
   const int band = v >= 0.0f ? (int)fminf(v * (1.0f / 16.0f), (float)(kOrderBands - 1)) : 0;  // NaN: 0
   return ((f >= 0 && f < nf) ? (int)f : nf - 1) * kOrderBands + band;
 }
-__device__ inline void edge_order_block(const OrderIn& q, const int64_t* __restrict__ jj, int E,
-                                        int N2, int* __restrict__ order, int* bins) {
+// Keys of the groups after the first (E > 4 T only: recomputed in both
+// passes), counted (order == null) or scattered.  One call site per pass
+// behind an E > 4 T branch: the graphs of the update step (E <= 4 T) run
+// straight through one copy of the key arithmetic.
+__device__ __forceinline__ void edge_order_rest(const OrderIn& q, const int64_t* __restrict__ jj, int E,
+                                             int nf, int* __restrict__ order, int* bins) {
   const int tid = threadIdx.x, T = blockDim.x;
-  const int nf = min(max(N2, 1), kOrderBins / kOrderBands), nb = nf * kOrderBands;
-  if (E <= 0) return;
-  // keys of 4 edges (tid + 4 T k + r T) at a time, every load of the four
-  // issued before the first use; the first group's keys stay in registers
-  // for the scatter pass (E <= 4 T: no recomputation, cfg2)
-  auto keys4 = [&](int e0, int (&k)[4]) __attribute__((always_inline)) {
+  for (int e0 = tid + 4 * T; e0 < E; e0 += 4 * T) {
+    int k[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) k[r] = edge_order_key(q, jj, min(e0 + r * T, E - 1), nf);
-  };
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      if (e0 + r * T >= E) continue;
+      const int p = atomicAdd(&bins[k[r]], 1);
+      if (order) order[p] = e0 + r * T;
+    }
+  }
+}
+constexpr int kOrderLds = kOrderBins + 1 + 16;  // bins + the scan's wave totals (<= 1024 threads)
+__device__ inline void edge_order_block(const OrderIn& q, const int64_t* __restrict__ jj, int E,
+                                        int N2, int* __restrict__ order, int* bins) {
+  const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wid = tid >> 6;
+  const int nf = min(max(N2, 1), kOrderBins / kOrderBands), nb = nf * kOrderBands;
+  int* scr = bins + kOrderBins + 1;
+  if (E <= 0) return;
+  // keys of the thread's first 4 edges (tid + r T), every load of the four
+  // issued before the first use; they stay in registers for the scatter
   int k0[4];
-  keys4(tid, k0);
+#pragma unroll
+  for (int r = 0; r < 4; r++) k0[r] = edge_order_key(q, jj, min(tid + r * T, E - 1), nf);
   for (int b = tid; b <= nb; b += T) bins[b] = 0;
-  __syncthreads();
-  for (int e0 = tid; e0 < E; e0 += 4 * T) {
-    int k[4];
-    if (e0 == tid) {
+  lds_barrier();
 #pragma unroll
-      for (int r = 0; r < 4; r++) k[r] = k0[r];
-    } else {
-      keys4(e0, k);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-      if (e0 + r * T < E) atomicAdd(&bins[k[r]], 1);
+  for (int r = 0; r < 4; r++)
+    if (tid + r * T < E) atomicAdd(&bins[k0[r]], 1);
+  if (__builtin_expect(E > 4 * T, 0)) edge_order_rest(q, jj, E, nf, nullptr, bins);
+  lds_barrier();
+  // exclusive scan of the nb <= 1024 bins by every wave: a run of `per` bins
+  // per thread, one DPP scan per wave, the wave totals through LDS
+  const int per = (nb + T - 1) / T, b0 = min(tid * per, nb), b1 = min(b0 + per, nb);
+  int sum = 0;
+  for (int b = b0; b < b1; b++) sum += bins[b];
+  const int incl = wave_incl_sum(sum);
+  if (lane == 63) scr[wid] = incl;
+  lds_barrier();
+  int run = incl - sum;
+  for (int w = 0; w < wid; w++) run += scr[w];
+  for (int b = b0; b < b1; b++) {
+    const int c = bins[b];
+    bins[b] = run;
+    run += c;
   }
-  __syncthreads();
-  if (tid < 64) {  // exclusive scan of nb <= 1024 bins by one wave
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += 64) {
-      const int b = b0 + tid;
-      const int c = (b < nb) ? bins[b] : 0;
-      int x = c;
+  lds_barrier();
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (tid >= o) x += y;
-      }
-      if (b < nb) bins[b] = carry + x - c;
-      carry += __shfl(x, 63, 64);
-    }
-  }
-  __syncthreads();
-  for (int e0 = tid; e0 < E; e0 += 4 * T) {
-    int k[4];
-    if (e0 == tid) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) k[r] = k0[r];
-    } else {
-      keys4(e0, k);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-      if (e0 + r * T < E) order[atomicAdd(&bins[k[r]], 1)] = e0 + r * T;
-  }
+  for (int r = 0; r < 4; r++)
+    if (tid + r * T < E) order[atomicAdd(&bins[k0[r]], 1)] = tid + r * T;
+  if (__builtin_expect(E > 4 * T, 0)) edge_order_rest(q, jj, E, nf, order, bins);
 }
 
 }  // namespace dpvo

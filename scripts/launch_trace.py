@@ -42,7 +42,7 @@ def ba_phases(m, iters=2):
     return {k: v * 0.01 for k, v in d.items()}
 
 
-PHASES = ["edge pass", "histogram", "local scan", "scatter", "block work", "rank + stores"]
+PHASES = ["loads + zeroing", "edges + histogram", "scan", "scatter", "block work", "rank + stores"]
 
 
 def main():
@@ -117,9 +117,13 @@ def main():
     # workgroups >= 256 carry no marks (the launch stamps blockIdx < 256 only;
     # the rows past 256 hold other marks): the timeline covers the first 256
     nwg = min(256, int(max((r[:256, 0] > 0).sum() for r in rows)))
-    roles = {"plan shards": range(0, nps), "edge order": range(nps, nps + 1),
-             "reprojection": range(nps + 1, nps + 1 + nrep),
-             "insertion": range(nps + 1 + nrep, nwg)}
+    # the chains (plan shards, then the edge order) run on the blocks of XCDs 0
+    # and 1: chain c on block 8 (c // 2) + c % 2 (ba_window.hip launch_chain);
+    # the other blocks, in order: reprojection, then insertion tiles
+    chain = [8 * (c // 2) + c % 2 for c in range(nps + 1)]
+    rest = [b for b in range(nwg) if b not in chain]
+    roles = {"plan shards": chain[:nps], "edge order": chain[nps:],
+             "reprojection": rest[:nrep], "insertion": rest[nrep:]}
     print(f"{args.config}: E={E} marked workgroups={nwg} (plan {nps}, order 1, reprojection "
           f"{nrep}, insertion {nwg - nps - 1 - nrep} of the launch's first 256)")
     stats = {k: [] for k in roles}

@@ -1,6 +1,6 @@
 """Phase stamps of the sharded BA plan (shard 0, 100 MHz wall clock): edge
-pass (loads + kmin/kmax/fmin), presence bitmap + local histogram, local scan,
-scatter, rank + stores -- alone (fastba.plan) and inside the fused
+loads + zeroing, edges (kmin/kmax/fmin) + histogram, scan, scatter, block
+work, rank + stores -- alone (fastba.plan) and inside the fused
 insert + reproject + order + plan launch.
 
     python scripts/plan_phases.py [cfg2|dpvo25 ...]
@@ -17,7 +17,7 @@ import torch  # noqa: E402
 from dpvo_amd import fastba, synthetic  # noqa: E402
 from dpvo_amd._native import load_extension  # noqa: E402
 
-NAMES = ["edge pass", "presence + histogram", "local scan", "scatter", "block work", "rank + stores"]
+NAMES = ["loads + zeroing", "edges + histogram", "scan", "scatter", "block work", "rank + stores"]
 
 
 def stamps(cb, ws, E, t0, t1):
