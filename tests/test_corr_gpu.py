@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 from conftest import golden
+from corr_cases import _case, _close, _close_f16, _t, _wide
 
 import oracle
 
@@ -23,43 +24,12 @@ def cc(gpu):
     return dpvo_amd.load_extension("cuda_corr")
 
 
-def _t(a, dev, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return t.to(dtype) if dtype is not None else t
-
-
-def _close(out, ref, tol=1e-5):
-    ref = np.asarray(ref, np.float64)
-    out = np.asarray(out, np.float64)
-    assert out.shape == ref.shape
-    err = np.abs(out - ref).max() if ref.size else 0.0
-    assert err <= tol * max(1.0, np.abs(ref).max() if ref.size else 1.0), err
-
-
 @pytest.mark.parametrize("name", ["corr_loop_a", "corr_loop_b", "corr_loop_c", "corr_gs_a"])
 def test_forward_matches_reference_golden(cc, gpu, name):
     z = golden(name)
     out, = cc.forward(_t(z["fmap1"], gpu), _t(z["fmap2"], gpu), _t(z["coords"], gpu),
                       _t(z["ii"], gpu), _t(z["jj"], gpu), int(z["radius"]))
     _close(out.cpu().numpy(), z["out"], 1e-5 if name != "corr_gs_a" else 2e-5)
-
-
-def _case(seed, B=1, M=37, C=128, N1=9, N2=4, H2=24, W2=32, p=3, R=3, spread=0.3, far=0.1,
-          Hp=None, Wp=None):
-    r = np.random.default_rng(seed)
-    Hp = Hp or p
-    Wp = Wp or p
-    f1 = (0.25 * r.standard_normal((B, N1, C, Hp, Wp))).astype(np.float32)
-    f2 = (0.25 * r.standard_normal((B, N2, C, H2, W2))).astype(np.float32)
-    cx = r.uniform(-4, W2 + 4, (B, M, 1, 1))
-    cy = r.uniform(-4, H2 + 4, (B, M, 1, 1))
-    gx = np.arange(Wp)[None, None, None, :] - Wp // 2 + spread * r.standard_normal((B, M, Hp, Wp))
-    gy = np.arange(Hp)[None, None, :, None] - Hp // 2 + spread * r.standard_normal((B, M, Hp, Wp))
-    co = np.stack([cx + gx, cy + gy], 2).astype(np.float32)
-    co[:, : int(far * M), 0] += 5 * W2  # windows completely outside the map
-    ii = r.integers(0, N1, M)
-    jj = r.integers(0, N2, M)
-    return f1, f2, co, ii, jj, R
 
 
 @pytest.mark.parametrize("kw", [
@@ -138,16 +108,52 @@ def test_forward_empty(cc, gpu):
     assert out.shape == (1, 0, 7, 7, 3, 3)
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(spread=4.0), dict(R=1, M=9)])
-def test_backward_matches_oracle(cc, gpu, kw):
-    f1, f2, co, ii, jj, R = _case(6, **{**dict(M=19, C=32), **kw})
+def _bwd_grad(f1, co, R):
     Dp = 2 * R + 1
-    G = np.random.default_rng(7).standard_normal((1, len(ii), Dp, Dp, 3, 3)).astype(np.float32)
+    shape = (co.shape[0], co.shape[1], Dp, Dp) + f1.shape[3:]
+    return np.random.default_rng(7).standard_normal(shape).astype(np.float32)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(), dict(spread=4.0), dict(R=1, M=9),
+    dict(p=1), dict(p=2), dict(p=4),         # every NPT instantiation
+    dict(Hp=2, Wp=3),                        # np != NPT
+    dict(R=0), dict(R=2), dict(R=7),
+    dict(B=2, M=11),
+    dict(H2=5, W2=6),                        # tiny map: every window clipped
+    dict(far=0.5),                           # windows outside the map: no gradient
+    dict(C=5), dict(C=128),
+    dict(M=300, N1=2, N2=1),                 # contention: 150 edges per patch, 300 on one frame
+])
+def test_backward_matches_oracle(cc, gpu, kw):
+    """The contention case (M = 300, N1 = 2, N2 = 1) holds the same 1e-5 bar
+    (measured on an MI355X: 3.8e-7 / 1.9e-7 of max|ref| for fmap1 / fmap2; the
+    largest of the table is R = 7 at 7.4e-7)."""
+    f1, f2, co, ii, jj, R = _case(6, **{**dict(M=19, C=32), **kw})
+    G = _bwd_grad(f1, co, R)
     g1, g2 = cc.backward(_t(f1, gpu), _t(f2, gpu), _t(co, gpu), _t(ii, gpu), _t(jj, gpu),
                          _t(G, gpu), R)
     r1, r2 = oracle.corr_bwd(f1, f2, co, ii, jj, G, R)
+    print("bwd err / max|ref|", kw, np.abs(g1.cpu().numpy() - r1).max() / np.abs(r1).max(),
+          np.abs(g2.cpu().numpy() - r2).max() / np.abs(r2).max())
     _close(g1.cpu().numpy(), r1, 1e-5)
     _close(g2.cpu().numpy(), r2, 1e-5)
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(spread=4.0)])
+def test_backward_fp16_inputs(cc, gpu, kw):
+    """fp16 features: the extension accumulates in fp32 and casts the result
+    to fp16, so against the oracle on the fp16-rounded inputs one fp16
+    rounding of each value plus fp32 summation noise remains (_close_f16)."""
+    f1, f2, co, ii, jj, R = _case(6, **{**dict(M=19, C=32), **kw})
+    h1, h2 = f1.astype(np.float16), f2.astype(np.float16)
+    G = _bwd_grad(f1, co, R)
+    g1, g2 = cc.backward(_t(h1, gpu), _t(h2, gpu), _t(co, gpu), _t(ii, gpu), _t(jj, gpu),
+                         _t(G, gpu), R)
+    assert g1.dtype == torch.float16 and g2.dtype == torch.float16
+    r1, r2 = oracle.corr_bwd(h1.astype(np.float32), h2.astype(np.float32), co, ii, jj, G, R)
+    _close_f16(g1.float().cpu().numpy(), r1)
+    _close_f16(g2.float().cpu().numpy(), r2)
 
 
 @pytest.mark.parametrize("name", ["patchify_a", "patchify_b", "patchify_c"])
@@ -385,6 +391,43 @@ def test_insert_frame_fp16(gpu, H, W, scales):
         assert bool((p[0, [0, 2]] == 7.0).all())
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("H,W", [(8, 16), (9, 17), (37, 45)])
+@pytest.mark.parametrize("C", [24, 37, 130])
+def test_insert_frame_other_channel_counts(gpu, C, H, W, dtype):
+    """C != 128: channel groups past C (`gc >= C`), the scalar store of
+    C % 4 != 0 and partial 32-channel tiles; maps of one tile, one tile plus a
+    pixel, and ragged.  Bit-exact against avg_pool2d + copy with the other
+    slots untouched, for a host slot and for device slots of every sign
+    (slot = ((s % mem) + mem) % mem)."""
+    from dpvo_amd import altcorr, synthetic
+
+    scales, mem = (1, 2, 4, 8), 4
+    g = torch.Generator(device="cpu").manual_seed(100 * C + H)
+    fmap = torch.randn(C, H, W, generator=g).to(gpu).to(dtype)
+    refs = [fmap if s == 1 else
+            torch.nn.functional.avg_pool2d(fmap[None].float(), s, s)[0].to(dtype) for s in scales]
+
+    def ring():
+        return [synthetic.channels_last(torch.full((1, mem, C, H // s, W // s), 7.0, device=gpu,
+                                                   dtype=dtype)) for s in scales]
+
+    def check(pyr, slot):
+        others = [k for k in range(mem) if k != slot]
+        for p, s, ref in zip(pyr, scales, refs):
+            assert torch.equal(p[0, slot], ref), (s, slot)
+            assert bool((p[0, others] == 7.0).all()), (s, slot)
+
+    pyr = ring()
+    altcorr.insert_frame(fmap, pyr, 2, scales)
+    check(pyr, 2)
+    for sd in (0, mem - 1, mem, 3 * mem + 2, -1):
+        pyr = ring()
+        altcorr.insert_frame_ring(fmap, pyr, torch.tensor([sd], dtype=torch.int32, device=gpu),
+                                  scales)
+        check(pyr, ((sd % mem) + mem) % mem)
+
+
 # ---- NCHW fp16 levels: matrix-core path (corr_nchw.hip) ----
 # DPVO's own pyramid (dpvo.py:111-112: contiguous NCHW, fp16 under the default
 # MIXED_PRECISION) through the unchanged per-level entry.  fp16 x fp16
@@ -392,15 +435,6 @@ def test_insert_frame_fp16(gpu, H, W, scales):
 # once to fp16, so against the fp64 oracle on the same fp16 inputs each value
 # is within one fp16 rounding (2^-11 relative, 2^-10 allowed) plus fp32
 # summation noise (2e-5 of max|ref|).
-def _close_f16(out, ref):
-    out = np.asarray(out, np.float64)
-    ref = np.asarray(ref, np.float64)
-    assert out.shape == ref.shape
-    tol = 2.0 ** -10 * np.abs(ref) + 2e-5 * max(1.0, np.abs(ref).max() if ref.size else 1.0)
-    bad = np.abs(out - ref) > tol
-    assert not bad.any(), (np.abs(out - ref).max(), int(bad.sum()))
-
-
 def _f16_inputs(f1, f2):
     return f1.astype(np.float16), f2.astype(np.float16)
 
@@ -534,27 +568,6 @@ def test_nchw_fp32_cfg2_matches_channels_last(cc, gpu):
 
 # ---- fp32 features over a wide dynamic range: the
 # channels-last fp32 path must hold the fp32 bar whatever the magnitudes
-def _wide(seed, kind):
-    f1, f2, co, ii, jj, R = _case(seed, M=96, C=128, H2=40, W2=48)
-    r = np.random.default_rng(seed + 7)
-    if kind == "channel_scales":  # per-channel scales 1e-4 .. 1e3 on both sides
-        f1 = f1 * 10.0 ** r.uniform(-4, 3, (1, 1, 128, 1, 1))
-        f2 = f2 * 10.0 ** r.uniform(-4, 3, (1, 1, 128, 1, 1))
-    elif kind == "tiny":  # every feature ~1e-4 (f16-subnormal territory)
-        f1, f2 = f1 * 1e-4, f2 * 1e-4
-    elif kind == "large_a_tiny_b":
-        f1, f2 = f1 * 1e3, f2 * 1e-4
-    elif kind == "f16_edges":  # magnitudes at 2^-24, 2^-14, 2^-3, 1, 16
-        e = r.choice([-24, -14, -3, 0, 4], size=f2.shape)
-        f2 = np.sign(f2) * 2.0 ** e * (1 + 0.01 * r.standard_normal(f2.shape))
-        e1 = r.choice([-14, -3, 0], size=f1.shape)
-        f1 = np.sign(f1) * 2.0 ** e1 * (1 + 0.01 * r.standard_normal(f1.shape))
-    elif kind == "beyond_f16":  # |b| >= 65520 in some pixels of the fine level
-        m = r.random(f2.shape) < 0.02
-        f2 = np.where(m, np.sign(f2) * r.uniform(65520, 3e5, f2.shape), f2)
-    return f1.astype(np.float32), f2.astype(np.float32), co, ii, jj, R
-
-
 @pytest.mark.parametrize("kind", ["channel_scales", "tiny", "large_a_tiny_b", "f16_edges",
                                   "beyond_f16"])
 def test_channels_last_fp32_wide_range(gpu, kind):
