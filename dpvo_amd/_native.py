@@ -1,9 +1,10 @@
 """Loader for the in-tree native build (dpvo_amd/_native/).
 
-The three extension modules keep the reference's module names -- cuda_corr,
+Three extension modules keep the reference's module names -- cuda_corr,
 cuda_ba, lietorch_backends (setup.py:12-37 of cuteboyqq/DPVO) -- so that code
 written against the reference (`import cuda_corr`) finds them once
-dpvo_amd is imported.  There is no fallback: if the build is missing the
+dpvo_amd is imported; dpvo_update (the update operator, PyTorch in the
+reference) is this build's own.  There is no fallback: if the build is missing the
 import fails loudly with the command that produces it.
 """
 from __future__ import annotations
@@ -15,7 +16,7 @@ import sys
 
 NATIVE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_native")
 LIB_PATH = os.path.join(NATIVE_DIR, "libdpvo_hot.so")
-EXT_NAMES = ("cuda_corr", "cuda_ba", "lietorch_backends")
+EXT_NAMES = ("cuda_corr", "cuda_ba", "lietorch_backends", "dpvo_update")
 
 _BUILD_HINT = "build it with `python -m dpvo_amd.build` (hipcc --offload-arch=gfx950)"
 
@@ -61,6 +62,8 @@ def c_abi():
         _lib.dpvo_version.restype = ctypes.c_char_p
         _lib.dpvo_status_string.restype = ctypes.c_char_p
         _lib.dpvo_ba_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_update_packed_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_update_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 
 

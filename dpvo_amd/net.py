@@ -1,0 +1,145 @@
+"""DPVO's update operator (dpvo/net.py:175-339) on the MI355X.
+
+``Update`` has the reference module's parameter names, so a DPVO checkpoint's
+``update.*`` keys load unchanged, and the reference's call signature; the
+forward pass is the fused HIP operator of csrc/update_op.hip (inference only).
+The parameters stay fp32 tensors; ``dtype`` chooses how they are packed for
+the matrix cores: ``torch.float16`` (fp16 operands, fp32 accumulation) or
+``torch.float32`` (exact fp32 products).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from ._native import load_extension, require_gpu
+
+DIM = 384
+
+_ext = None
+
+
+def ext():
+    global _ext
+    if _ext is None:
+        _ext = load_extension("dpvo_update")
+    return _ext
+
+
+class _GatedResidual(nn.Module):  # blocks.py:15-29 (parameters only)
+    def __init__(self, dim):
+        super().__init__()
+        self.gate = nn.Sequential(nn.Linear(dim, dim), nn.Sigmoid())
+        self.res = nn.Sequential(nn.Linear(dim, dim), nn.ReLU(inplace=True), nn.Linear(dim, dim))
+
+
+class _SoftAgg(nn.Module):  # blocks.py:31-38 / net.py:671-676 (parameters only)
+    def __init__(self, dim):
+        super().__init__()
+        self.f = nn.Linear(dim, dim)
+        self.g = nn.Linear(dim, dim)
+        self.h = nn.Linear(dim, dim)
+
+
+def _mlp(i, o):
+    return nn.Sequential(nn.Linear(i, o), nn.ReLU(inplace=True), nn.Linear(o, o))
+
+
+class Update(nn.Module):
+    """Drop-in for ``dpvo.net.Update`` (inference).
+
+    forward(net, inp, corr, flow, ii, jj, kk, ix=None, jx=None, gk=None, gij=None)
+    -> (net, (d, w, None)), shapes [1, E, .] as in the reference.  ix / jx
+    default to ``fastba.neighbors(kk, jj)`` (-1 = missing, masked), gk to kk and
+    gij to ``ii * 12345 + jj``: the original DPVO.  For the fork's live Update
+    pass ``ix, jx = neighbors_tensor(kk, jj)`` and ``gij=ii``.
+    """
+
+    def __init__(self, p=3, dtype=torch.float16, corr_dim=None):
+        super().__init__()
+        if dtype not in (torch.float16, torch.float32):
+            raise ValueError("Update: dtype (the packed weight type) is float16 or float32")
+        self.wdtype = dtype
+        self.corr_dim = int(corr_dim) if corr_dim is not None else 2 * 49 * p * p
+        self.c1 = _mlp(DIM, DIM)
+        self.c2 = _mlp(DIM, DIM)
+        self.norm = nn.LayerNorm(DIM, eps=1e-3)
+        self.agg_kk = _SoftAgg(DIM)
+        self.agg_ij = _SoftAgg(DIM)
+        self.gru = nn.Sequential(nn.LayerNorm(DIM, eps=1e-3), _GatedResidual(DIM),
+                                 nn.LayerNorm(DIM, eps=1e-3), _GatedResidual(DIM))
+        self.corr = nn.Sequential(nn.Linear(self.corr_dim, DIM), nn.ReLU(inplace=True),
+                                  nn.Linear(DIM, DIM), nn.LayerNorm(DIM, eps=1e-3),
+                                  nn.ReLU(inplace=True), nn.Linear(DIM, DIM))
+        self.d = nn.Sequential(nn.ReLU(inplace=False), nn.Linear(DIM, 2), nn.Identity())
+        self.w = nn.Sequential(nn.ReLU(inplace=False), nn.Linear(DIM, 2), nn.Identity(),
+                               nn.Sigmoid())
+        self._blob = None
+        self._blob_key = None
+        self._ws = None
+
+    @classmethod
+    def from_reference(cls, module, dtype=torch.float16):
+        """Copy an existing reference ``Update`` (any device / dtype)."""
+        sd = {k: v.detach().to("cpu", torch.float32) for k, v in module.state_dict().items()}
+        new = cls(dtype=dtype, corr_dim=sd["corr.0.weight"].shape[1])
+        new.load_state_dict(sd)
+        return new
+
+    # -- packed weights ------------------------------------------------------
+    def _wcode(self):
+        return ext().F16 if self.wdtype == torch.float16 else ext().F32
+
+    def _key(self, device):
+        return (str(device), self.wdtype) + tuple((p.data_ptr(), p._version)
+                                                  for p in self.parameters())
+
+    def packed(self, device):
+        """The device blob of the packed weights; packed on first use and again
+        whenever a parameter was written or replaced."""
+        key = self._key(device)
+        if self._blob is None or key != self._blob_key:
+            tensors = [p.detach().to("cpu", torch.float32).contiguous() for p in self.parameters()]
+            if len(tensors) != 50:
+                raise RuntimeError("Update: expected 50 parameter tensors")
+            host = ext().pack_weights(tensors, self.corr_dim, self._wcode())
+            self._blob = host.to(device)
+            self._blob_key = key
+        return self._blob
+
+    def workspace(self, E, device):
+        need = ext().workspace_bytes(E, self.corr_dim)
+        if self._ws is None or self._ws.device != device or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._ws
+
+    @torch.no_grad()
+    def forward(self, net, inp, corr, flow, ii, jj, kk, ix=None, jx=None, gk=None, gij=None):
+        require_gpu(net)
+        if net.dim() != 3 or net.shape[0] != 1 or net.shape[2] != DIM:
+            raise ValueError("Update: net must be [1, E, 384]")
+        E, dev = net.shape[1], net.device
+        if corr.shape[-1] != self.corr_dim:
+            raise ValueError(f"Update: corr has {corr.shape[-1]} features, the module "
+                             f"{self.corr_dim}")
+        ii, jj, kk = (t.reshape(-1).long() for t in (ii, jj, kk))
+        if ix is None or jx is None:
+            from . import fastba
+
+            ix, jx = fastba.neighbors(kk, jj)
+        gk = kk if gk is None else gk
+        gij = ii * 12345 + jj if gij is None else gij
+        io = net.dtype
+        net_out = torch.empty_like(net, memory_format=torch.contiguous_format)
+        d = torch.empty(1, E, 2, dtype=torch.float32, device=dev)
+        w = torch.empty(1, E, 2, dtype=torch.float32, device=dev)
+        if E == 0:
+            return net_out, (d, w, None)
+        blob, ws = self.packed(dev), self.workspace(E, dev)
+        x = ext()
+        x.plan(gk.reshape(-1).long(), gij.reshape(-1).long(), ws)
+        x.forward(blob, self._wcode(), net.reshape(E, DIM).contiguous(),
+                  inp.reshape(E, DIM).to(io).contiguous(),
+                  corr.reshape(E, self.corr_dim).to(io).contiguous(), ix.reshape(-1).long(),
+                  jx.reshape(-1).long(), ws, net_out.view(E, DIM), d.view(E, 2), w.view(E, 2))
+        return net_out, (d, w, None)

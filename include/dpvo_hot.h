@@ -566,6 +566,77 @@ int dpvo_edges_loop(const float* poses, const float* patches, const float* intri
                     int32_t* out_n, int32_t* errors, void* stream);
 size_t dpvo_edges_loop_work_floats(void);
 
+/* --------------------------------------------------------- update operator */
+
+/* DPVO's update operator, inference only (dpvo/net.py:175-339 `Update`, with
+   blocks.py:15-29 GatedResidual and net.py:671-714 SoftAggONNX / blocks.py:31-48
+   SoftAgg), as fused kernels on the matrix cores.  dim must be 384.
+
+     t  = corr MLP(corr)                       net.py:201-208
+     x  = LN(net + inp + t)                    net.py:283-284
+     x += c1(m_ix * x[ix]); x += c2(m_jx * x[jx])          net.py:305-306 (265-266)
+     x += h_kk(sum_group softmax_group(g_kk(x)) f_kk(x))[group]   net.py:319
+     x += h_ij(...)                                         net.py:320
+     x  = gru(x); d = d(x); w = w(x)           net.py:322-326
+
+   ix / jx and the group ids are inputs, so one operator serves the original
+   DPVO (fastba.neighbors, -1 = missing and masked; groups kk and
+   ii * 12345 + jj) and the fork's live Update (neighbors_tensor, always in
+   range; groups kk and ii).  An index outside [0, E) is a missing neighbour.
+   The group softmax subtracts the per-(group, channel) maximum
+   (torch_scatter.scatter_softmax); there is no +-50 clamp and no ii * 1e-10
+   term on d and w (net.py:692, 331-337).
+
+   Weights are DPVO_F32 (exact fp32 products, v_mfma_f32_16x16x4_f32) or
+   DPVO_F16 (v_mfma_f32_16x16x32_f16: activations rounded to fp16 only as
+   matrix operands, fp32 accumulation); everything between the linears is
+   fp32.  Group sums run in ascending edge order: results are deterministic. */
+
+/* Bytes of the packed weight blob; 0 for K0 < 1 or a wdtype other than
+   DPVO_F32 / DPVO_F16.  K0 = corr_dim = 2 * 49 * p * p (net.py:202). */
+size_t dpvo_update_packed_bytes(int K0, int wdtype);
+
+/* HOST function: packs the 50 parameter tensors of Update (fp32, PyTorch
+   layout, host pointers, in state_dict order: c1.0.weight, c1.0.bias,
+   c1.2.*, c2.0.*, c2.2.*, norm.*, agg_kk.f.*, .g.*, .h.*, agg_ij.f.*, .g.*,
+   .h.*, gru.0.*, gru.1.gate.0.*, gru.1.res.0.*, gru.1.res.2.*, gru.2.*,
+   gru.3.gate.0.*, gru.3.res.0.*, gru.3.res.2.*, corr.0.*, corr.2.*, corr.3.*,
+   corr.5.*, d.1.*, w.1.*) into a host blob of dpvo_update_packed_bytes()
+   bytes (layout: csrc/update_op.hip).  fp16 weights are rounded to nearest
+   even; the first layer's K tail (K0 up to a multiple of 128) is zero.  Pack
+   once at load and upload the blob.  dim != 384 or a bad wdtype:
+   DPVO_ERR_UNSUPPORTED; ntensors != 50, null pointers, K0 < 1:
+   DPVO_ERR_INVALID; blob_size too small: DPVO_ERR_WORKSPACE. */
+int dpvo_update_pack_weights(const float* const* tensors, int ntensors, int dim, int K0,
+                             int wdtype, void* blob, size_t blob_size);
+
+/* Bytes of the caller-owned device workspace of one E (scratch rows f, g, the
+   second x buffer, the group rows, and the group plan); 0 for E < 1 or K0 < 1. */
+size_t dpvo_update_workspace_bytes(int E, int K0);
+
+/* Group plan of the two aggregations (replaces torch.unique(ix,
+   return_inverse=True), blocks.py:41, and the [H, H] equality mask of
+   net.py:695-702), built on the device without a host sync: per edge the
+   dense group index (groups numbered by their smallest member edge), member
+   lists in ascending edge order, and the group count, all kept in the
+   workspace.  gk, gij: int64 [E] group ids (any values).  Valid until the ids
+   change; dpvo_update_forward of the same E and workspace reads it. */
+int dpvo_update_plan(const int64_t* gk, const int64_t* gij, int E, void* workspace,
+                     size_t workspace_size, void* stream);
+
+/* The operator (replaces Update.forward, net.py:221-339).  blob: device copy
+   of the packed weights of (K0, wdtype).  net, inp [E, 384], corr [E, K0],
+   net_out [E, 384] in iodtype (DPVO_F32, or DPVO_F16 with DPVO_F16 weights);
+   ix, jx int64 [E]; d, w fp32 [E, 2].  net_out may alias net.  No allocation,
+   nine plain launches on `stream` (capturable).  E <= 0: DPVO_OK without a
+   launch; dim != 384 or an unsupported dtype pair: DPVO_ERR_UNSUPPORTED; null
+   pointers, K0 < 1: DPVO_ERR_INVALID; short workspace: DPVO_ERR_WORKSPACE;
+   all checked before any launch. */
+int dpvo_update_forward(const void* blob, int wdtype, const void* net, const void* inp,
+                        const void* corr, const int64_t* ix, const int64_t* jx, int E, int dim,
+                        int K0, int iodtype, void* workspace, size_t workspace_size,
+                        void* net_out, float* d, float* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
