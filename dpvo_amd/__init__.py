@@ -6,6 +6,8 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
   cuda_ba            F-BA / F-REPROJ / F-NBR          -> dpvo_amd.fastba
   lietorch_backends  L-SE3 (SO3 / SE3)                -> dpvo_amd.lietorch
   (net.py Update)    the update operator              -> dpvo_amd.net.Update
+  (net.py Patchifier, extractor.py BasicEncoder4)     -> dpvo_amd.Patchifier,
+                     the feature encoders and gathers    dpvo_amd.BasicEncoder4
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -14,4 +16,17 @@ from ._native import EXT_NAMES, NATIVE_DIR, c_abi, load_extension  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["altcorr", "fastba", "lietorch", "net", "projective_ops", "load_extension", "c_abi"]
+__all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "load_extension",
+           "c_abi", "BasicEncoder4", "Patchifier"]
+
+
+def __getattr__(name):  # the two classes, without importing torch.nn at package import
+    if name == "BasicEncoder4":
+        from .extractor import BasicEncoder4
+
+        return BasicEncoder4
+    if name == "Patchifier":
+        from .net import Patchifier
+
+        return Patchifier
+    raise AttributeError(f"module 'dpvo_amd' has no attribute {name!r}")

@@ -3,8 +3,8 @@
 Three extension modules keep the reference's module names -- cuda_corr,
 cuda_ba, lietorch_backends (setup.py:12-37 of cuteboyqq/DPVO) -- so that code
 written against the reference (`import cuda_corr`) finds them once
-dpvo_amd is imported; dpvo_update (the update operator, PyTorch in the
-reference) is this build's own.  There is no fallback: if the build is missing the
+dpvo_amd is imported; dpvo_update (the update operator) and dpvo_encoder (the
+feature encoders), PyTorch in the reference, are this build's own.  There is no fallback: if the build is missing the
 import fails loudly with the command that produces it.
 """
 from __future__ import annotations
@@ -16,7 +16,7 @@ import sys
 
 NATIVE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_native")
 LIB_PATH = os.path.join(NATIVE_DIR, "libdpvo_hot.so")
-EXT_NAMES = ("cuda_corr", "cuda_ba", "lietorch_backends", "dpvo_update")
+EXT_NAMES = ("cuda_corr", "cuda_ba", "lietorch_backends", "dpvo_update", "dpvo_encoder")
 
 _BUILD_HINT = "build it with `python -m dpvo_amd.build` (hipcc --offload-arch=gfx950)"
 
@@ -64,6 +64,8 @@ def c_abi():
         _lib.dpvo_ba_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_update_packed_bytes.restype = ctypes.c_size_t
         _lib.dpvo_update_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_encoder_packed_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_encoder_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 
 

@@ -9,6 +9,7 @@ Products (dpvo_amd/_native/, git-ignored, shipped to the GPU box by gpurun):
   lietorch_backends.<ext>             reference's module / function names,
                                       thin wrappers over libdpvo_hot.so
   dpvo_update.<ext>                   the update operator (PyTorch in the reference)
+  dpvo_encoder.<ext>                  the feature encoders (PyTorch in the reference)
 
 hipcc compiles the kernels directly for gfx950; the extension modules are
 host-only C++ compiled with g++ against the PyTorch-ROCm headers (no hipify,
@@ -32,12 +33,13 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("DPVO_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["corr.hip", "corr_nhwc.hip", "corr_nchw.hip", "ba.hip", "ba_window.hip", "ba_large.hip", "lie.hip", "pgo.hip", "pg.hip",
-               "keyframe.hip", "spd_solve.hip", "ransac.hip", "update_op.hip"]
+               "keyframe.hip", "spd_solve.hip", "ransac.hip", "update_op.hip", "encoder.hip"]
 EXTENSIONS = {
     "cuda_corr": "ext_cuda_corr.cpp",
     "cuda_ba": "ext_cuda_ba.cpp",
     "lietorch_backends": "ext_lietorch.cpp",
     "dpvo_update": "ext_update.cpp",
+    "dpvo_encoder": "ext_encoder.cpp",
 }
 HEADERS = ["common.hpp", "ext_common.hpp", "ba_device.hpp", "ba_solve.hpp", "pyr_insert.hpp", "ba_bgj.hpp",
            "sim3.hpp"]

@@ -1,4 +1,5 @@
-"""DPVO's update operator (dpvo/net.py:175-339) on the MI355X.
+"""DPVO's update operator (dpvo/net.py:175-339) and patchifier (net.py:344-407)
+on the MI355X.
 
 ``Update`` has the reference module's parameter names, so a DPVO checkpoint's
 ``update.*`` keys load unchanged, and the reference's call signature; the
@@ -143,3 +144,81 @@ class Update(nn.Module):
                   corr.reshape(E, self.corr_dim).to(io).contiguous(), ix.reshape(-1).long(),
                   jx.reshape(-1).long(), ws, net_out.view(E, DIM), d.view(E, 2), w.view(E, 2))
         return net_out, (d, w, None)
+
+
+class Patchifier(nn.Module):
+    """Drop-in for ``dpvo.net.Patchifier`` (net.py:344-407, inference): the two
+    HIP encoders and the patch gathers.
+
+    forward(images [b, n, 3, H, W], ...) -> (fmap, gmap, imap, patches, index
+    [, clr]) as in the reference.  ``coords`` ([n, M, 2] float, integer-valued
+    (x, y) centres at quarter resolution, 1 <= x <= w - 2, 1 <= y <= h - 2)
+    replaces the random draw when given.
+    """
+
+    def __init__(self, patch_size=3, dtype=torch.float16):
+        super().__init__()
+        from .extractor import BasicEncoder4
+
+        self.patch_size = patch_size
+        self.fnet = BasicEncoder4(output_dim=128, norm_fn="instance", dtype=dtype)
+        self.inet = BasicEncoder4(output_dim=DIM, norm_fn="none", dtype=dtype)
+
+    @staticmethod
+    def _image_gradient(images):  # net.py:351-357
+        gray = ((images + 0.5) * (255.0 / 2)).sum(dim=2)
+        dx = gray[..., :-1, 1:] - gray[..., :-1, :-1]
+        dy = gray[..., 1:, :-1] - gray[..., :-1, :-1]
+        g = torch.sqrt(dx ** 2 + dy ** 2)
+        return torch.nn.functional.avg_pool2d(g, 4, 4)
+
+    @torch.no_grad()
+    def forward(self, images, patches_per_image=80, disps=None, centroid_sel_strat="RANDOM",
+                return_color=False, coords=None):
+        from . import altcorr
+
+        require_gpu(images)
+        fmap = self.fnet(images)  # the / 4 of net.py:361-362 is inside the encoders
+        imap = self.inet(images)
+        b, n, c, h, w = fmap.shape
+        dev = images.device
+        P = self.patch_size
+        if coords is not None:
+            coords = coords.to(dev, torch.float32)
+            if coords.dim() != 3 or coords.shape[0] != n or coords.shape[2] != 2:
+                raise ValueError("Patchifier: coords must be [n, M, 2]")
+            patches_per_image = coords.shape[1]
+        elif centroid_sel_strat == "GRADIENT_BIAS":  # net.py:369-379
+            g = self._image_gradient(images)
+            x = torch.randint(1, w - 1, size=[n, 3 * patches_per_image], device=dev)
+            y = torch.randint(1, h - 1, size=[n, 3 * patches_per_image], device=dev)
+            cand = torch.stack([x, y], dim=-1).float()
+            g = altcorr.patchify(g[0, :, None].contiguous(), cand, 0).view(n, 3 * patches_per_image)
+            ix = torch.argsort(g, dim=1)
+            x = torch.gather(x, 1, ix[:, -patches_per_image:])
+            y = torch.gather(y, 1, ix[:, -patches_per_image:])
+            coords = torch.stack([x, y], dim=-1).float()
+        elif centroid_sel_strat == "RANDOM":
+            x = torch.randint(1, w - 1, size=[n, patches_per_image], device=dev)
+            y = torch.randint(1, h - 1, size=[n, patches_per_image], device=dev)
+            coords = torch.stack([x, y], dim=-1).float()
+        else:
+            raise NotImplementedError(
+                f"Patch centroid selection not implemented: {centroid_sel_strat}")
+
+        imap = altcorr.patchify(imap[0], coords, 0).view(b, -1, DIM, 1, 1)
+        gmap = altcorr.patchify(fmap[0], coords, P // 2).view(b, -1, 128, P, P)
+        if return_color:
+            clr = altcorr.patchify(images[0].float().contiguous(), 4 * (coords + 0.5), 0).view(b, -1, 3)
+        if disps is None:
+            disps = torch.ones(b, n, h, w, device=dev)
+        # (x, y, disps) per pixel: utils.py:39-54
+        ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32, device=dev),
+                                torch.arange(w, dtype=torch.float32, device=dev), indexing="ij")
+        grid = torch.stack([xs.expand(b, n, h, w), ys.expand(b, n, h, w),
+                            disps.to(dev, torch.float32)], dim=2)
+        patches = altcorr.patchify(grid[0].contiguous(), coords, P // 2).view(b, -1, 3, P, P)
+        index = torch.arange(n, device=dev).view(n, 1).repeat(1, patches_per_image).reshape(-1)
+        if return_color:
+            return fmap, gmap, imap, patches, index, clr
+        return fmap, gmap, imap, patches, index

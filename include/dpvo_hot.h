@@ -637,6 +637,68 @@ int dpvo_update_forward(const void* blob, int wdtype, const void* net, const voi
                         int K0, int iodtype, void* workspace, size_t workspace_size,
                         void* net_out, float* d, float* w, void* stream);
 
+/* ---------------------------------------------------------------------------
+   The feature encoders (replace BasicEncoder4, dpvo/extractor.py:200-264: the
+   fnet / inet of net.py's Patchifier).  Inference only.
+
+     x = relu(norm(conv1(img)))                 7x7 stride 2,  3 -> 32
+     x = layer1(x)                              two residual blocks, 32 -> 32
+     x = layer2(x)                              32 -> 64 stride 2 (skip: 1x1
+                                                stride-2 conv + norm), 64 -> 64
+     out = conv2(x) / 4                         1x1, 64 -> out_dim
+     block: y = relu(norm(conv3x3(x))); y = relu(norm(conv3x3(y)));
+            out = relu(skip(x) + y)
+
+   norm is the identity (DPVO_ENCODER_NORM_NONE, inet) or InstanceNorm2d with
+   its defaults (DPVO_ENCODER_NORM_INSTANCE, fnet: per image and channel over
+   the plane, biased variance, eps 1e-5, no affine).  H x W -> H1 x W1 -> h x w
+   with H1 = (H - 1) / 2 + 1, h = (H1 - 1) / 2 + 1.  The / 4 of Patchifier
+   (net.py:361-362) is part of the operator.
+
+   Weights are DPVO_F32 (exact fp32 products, v_mfma_f32_16x16x4_f32) or
+   DPVO_F16 (v_mfma_f32_16x16x32_f16: activations rounded to fp16 only as
+   matrix operands, fp32 accumulation); bias, statistics (combined in fp64 in
+   a fixed order), normalisation, ReLU, residual adds and the / 4 are fp32.
+   No float atomics: results are deterministic. */
+enum { DPVO_ENCODER_NORM_NONE = 0, DPVO_ENCODER_NORM_INSTANCE = 1 };
+enum { DPVO_ENCODER_NCHW = 0, DPVO_ENCODER_NHWC = 1 };
+
+/* Bytes of the packed weight blob; 0 for an out_dim that is not a multiple of
+   64 in [64, 1024] or a wdtype other than DPVO_F32 / DPVO_F16. */
+size_t dpvo_encoder_packed_bytes(int out_dim, int wdtype);
+
+/* HOST function: packs the 22 parameter tensors of BasicEncoder4 (fp32,
+   PyTorch layout [Cout, Cin, kh, kw], host pointers, in state_dict order:
+   conv1.weight, conv1.bias, layer1.0.conv1.*, layer1.0.conv2.*,
+   layer1.1.conv1.*, layer1.1.conv2.*, layer2.0.conv1.*, layer2.0.conv2.*,
+   layer2.0.downsample.0.*, layer2.1.conv1.*, layer2.1.conv2.*, conv2.*) into
+   a host blob of dpvo_encoder_packed_bytes() bytes (layout:
+   csrc/encoder.hip).  fp16 weights are rounded to nearest even.  Pack once at
+   load and upload the blob.  ntensors != 22 or null pointers:
+   DPVO_ERR_INVALID; a bad out_dim, norm or wdtype: DPVO_ERR_UNSUPPORTED;
+   blob_size too small: DPVO_ERR_WORKSPACE. */
+int dpvo_encoder_pack_weights(const float* const* tensors, int ntensors, int out_dim, int norm,
+                              int wdtype, void* blob, size_t blob_size);
+
+/* Bytes of the caller-owned device workspace (the intermediate channels-last
+   fp32 planes and the norm statistics); 0 for non-positive sizes, a bad
+   out_dim or sizes outside the kernels' index range. */
+size_t dpvo_encoder_workspace_bytes(int n_images, int H, int W, int out_dim);
+
+/* The encoder.  blob: device copy of the packed weights of (out_dim, norm,
+   wdtype).  images: fp32 [n_images, 3, H, W] contiguous, already scaled
+   (2 (img / 255) - 0.5, dpvo.py).  out: fp32 [n_images, out_dim, h, w], stored
+   NCHW-contiguous (DPVO_ENCODER_NCHW) or as channels-last memory
+   [n_images, h, w, out_dim] (DPVO_ENCODER_NHWC); the two hold the same values
+   bit for bit.  Any H, W, n_images >= 1.  No allocation; 11 (none) or 25
+   (instance) plain launches on `stream` (capturable).  Null pointers,
+   non-positive sizes, an unknown out_layout: DPVO_ERR_INVALID; a bad wdtype,
+   norm or out_dim, or sizes outside the index range: DPVO_ERR_UNSUPPORTED;
+   short workspace: DPVO_ERR_WORKSPACE; all checked before any launch. */
+int dpvo_encoder_forward(const void* blob, int wdtype, int norm, int out_dim, const float* images,
+                         int n_images, int H, int W, float* out, int out_layout, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
