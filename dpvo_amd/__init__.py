@@ -8,6 +8,7 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
   (net.py Update)    the update operator              -> dpvo_amd.net.Update
   (net.py Patchifier, extractor.py BasicEncoder4)     -> dpvo_amd.Patchifier,
                      the feature encoders and gathers    dpvo_amd.BasicEncoder4
+  (dpvo.py __call__ head, terminate / get_pose)      -> dpvo_amd.frontend
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -16,7 +17,7 @@ from ._native import EXT_NAMES, NATIVE_DIR, c_abi, load_extension  # noqa: F401
 
 __version__ = "0.1.0"
 
-__all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "load_extension",
+__all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "frontend", "load_extension",
            "c_abi", "BasicEncoder4", "Patchifier"]
 
 

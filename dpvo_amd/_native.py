@@ -66,6 +66,7 @@ def c_abi():
         _lib.dpvo_update_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_packed_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_trajectory_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 
 

@@ -1147,6 +1147,95 @@ void edges_loop(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrin
                "cuda_ba.edges_loop");
 }
 
+// The head of DPVO.__call__ (dpvo.py:931-965): tstamps / intrinsics / pose /
+// patches of frame row n, in place, one launch.  n / counter: the host value,
+// or the int32 device scalar when given.
+void frame_init(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics,
+                torch::Tensor tstamps, torch::Tensor times, torch::Tensor new_patches,
+                torch::Tensor new_intrinsics, int64_t M, int64_t n,
+                c10::optional<torch::Tensor> n_dev, int64_t counter,
+                c10::optional<torch::Tensor> counter_dev, int64_t motion_model, double damping,
+                double res, bool median) {
+  check_device(poses, "poses");
+  check_device(patches, "patches");
+  check_device(intrinsics, "intrinsics");
+  check_device(tstamps, "tstamps");
+  check_device(times, "times");
+  TORCH_CHECK(poses.scalar_type() == torch::kFloat32 && patches.scalar_type() == torch::kFloat32 &&
+                  intrinsics.scalar_type() == torch::kFloat32,
+              "poses / patches / intrinsics must be float32");
+  TORCH_CHECK(tstamps.scalar_type() == torch::kInt64, "tstamps must be int64 (long)");
+  TORCH_CHECK(times.scalar_type() == torch::kFloat64, "times must be float64");
+  TORCH_CHECK(poses.is_contiguous() && patches.is_contiguous() && intrinsics.is_contiguous() &&
+                  tstamps.is_contiguous() && times.is_contiguous(),
+              "the per-frame buffers and times must be contiguous (written / read in place)");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7 && poses.size(0) > 0, "poses: [N, 7]");
+  const int64_t N = poses.size(0);
+  TORCH_CHECK(patches.dim() == 4 && patches.size(1) == 3 && patches.size(2) == patches.size(3),
+              "patches: [N * M, 3, P, P]");
+  const int64_t P = patches.size(-1);
+  TORCH_CHECK(M > 0 && patches.size(0) == N * M, "patches: [N * M, 3, P, P] with N = ", N,
+              " frames of M = ", M);
+  TORCH_CHECK(intrinsics.numel() == 4 * N, "intrinsics: [N, 4]");
+  TORCH_CHECK(tstamps.numel() >= N, "tstamps: [N]");
+  TORCH_CHECK(times.dim() == 1 && times.numel() > 0 && times.numel() < (1LL << 31), "times: [cap]");
+  new_patches = f32_contig(new_patches, "new_patches");
+  new_intrinsics = f32_contig(new_intrinsics, "new_intrinsics");
+  TORCH_CHECK(new_patches.numel() == M * 3 * P * P, "new_patches: [M, 3, P, P]");
+  TORCH_CHECK(new_intrinsics.numel() == 4, "new_intrinsics: [4]");
+  TORCH_CHECK(N * M * 3 * P * P < (1LL << 40) && N < (1LL << 31) && M < (1LL << 31), "too large");
+  const int32_t* nd = (n_dev && n_dev->defined()) ? dev_scalar(*n_dev, "n") : nullptr;
+  const int32_t* cd =
+      (counter_dev && counter_dev->defined()) ? dev_scalar(*counter_dev, "counter") : nullptr;
+  TORCH_CHECK(nd || (n >= 0 && n < N), "frame_init: n = ", n, " outside [0, ", N, ")");
+  TORCH_CHECK(cd || (counter >= 0 && counter < times.numel()), "frame_init: counter = ", counter,
+              " outside times [0, ", times.numel(), ")");
+  check_status(dpvo_frame_init(poses.data_ptr<float>(), patches.data_ptr<float>(),
+                               intrinsics.data_ptr<float>(), tstamps.data_ptr<int64_t>(),
+                               times.data_ptr<double>(), (int)times.numel(),
+                               new_patches.data_ptr<float>(), new_intrinsics.data_ptr<float>(),
+                               (int)N, (int)M, (int)P, nd ? 0 : (int)n, nd, cd ? 0 : (int)counter,
+                               cd, (int)motion_model, damping, res, median ? 1 : 0,
+                               current_stream()),
+               "cuda_ba.frame_init");
+}
+
+// DPVO.terminate's interpolation (dpvo.py:385-417) -> [traj [counter, 7],
+// root [counter] int64, info int32[2] = {unresolved frames, ignored records}]
+std::vector<torch::Tensor> trajectory(torch::Tensor poses, torch::Tensor tstamps, int64_t n,
+                                      c10::optional<torch::Tensor> n_dev, torch::Tensor delta_log,
+                                      torch::Tensor delta_pairs, torch::Tensor delta_count,
+                                      int64_t counter, bool inverse) {
+  poses = f32_contig(poses, "poses");
+  tstamps = idx64(tstamps, "tstamps");
+  delta_log = f32_contig(delta_log, "delta log");
+  delta_pairs = idx64(delta_pairs, "delta pairs");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7 && poses.size(0) > 0, "poses: [N, 7]");
+  const int64_t N = poses.size(0);
+  TORCH_CHECK(tstamps.numel() >= N && N < (1LL << 31), "tstamps: [N]");
+  TORCH_CHECK(delta_log.numel() % 7 == 0, "delta log: [cap, 7]");
+  const int64_t cap = delta_log.numel() / 7;
+  TORCH_CHECK(delta_pairs.numel() == 2 * cap && cap < (1LL << 31), "delta pairs: [cap, 2]");
+  TORCH_CHECK(counter >= 0 && counter < (1LL << 30), "trajectory: counter = ", counter);
+  const int32_t* nd = (n_dev && n_dev->defined()) ? dev_scalar(*n_dev, "n") : nullptr;
+  TORCH_CHECK(nd || (n >= 0 && n <= N), "trajectory: n = ", n, " outside [0, ", N, "]");
+  const int32_t* dc = dev_scalar(delta_count, "delta count");
+  auto traj = torch::empty({counter, 7}, poses.options());
+  auto root = torch::empty({counter}, tstamps.options());
+  auto info = torch::zeros({2}, poses.options().dtype(torch::kInt32));
+  const size_t wsb = dpvo_trajectory_workspace_bytes((int)counter);
+  auto ws = torch::empty({(int64_t)(wsb / sizeof(double))}, poses.options().dtype(torch::kFloat64));
+  check_status(dpvo_trajectory(poses.data_ptr<float>(), tstamps.data_ptr<int64_t>(), (int)N,
+                               nd ? 0 : (int)n, nd, delta_log.data_ptr<float>(),
+                               delta_pairs.data_ptr<int64_t>(), dc, (int)cap, (int)counter,
+                               inverse ? 1 : 0, traj.data_ptr<float>(), root.data_ptr<int64_t>(),
+                               info.data_ptr<int32_t>(), ws.data_ptr(), wsb, current_stream()),
+               "cuda_ba.trajectory");
+  return {traj, root, info};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward", &ba_forward, "BA forward operator");
   m.def("neighbors", &ba_neighbors, "temporal neighboor indicies");
@@ -1206,6 +1295,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta_tstamps") = py::none(), py::arg("delta_count") = py::none());
   m.def("edges_loop", &edges_loop, "PatchGraph.edges_loop (patchgraph.py:65-91), device count");
   m.def("edges_loop_work_floats", []() { return (int64_t)dpvo_edges_loop_work_floats(); });
+  m.def("frame_init", &frame_init,
+        "the head of DPVO.__call__ (dpvo.py:931-965): tstamps, intrinsics / RES, motion-model "
+        "pose and median-depth patches of frame row n, one launch",
+        py::arg("poses"), py::arg("patches"), py::arg("intrinsics"), py::arg("tstamps"),
+        py::arg("times"), py::arg("new_patches"), py::arg("new_intrinsics"), py::arg("M"),
+        py::arg("n"), py::arg("n_dev"), py::arg("counter"), py::arg("counter_dev"),
+        py::arg("motion_model"), py::arg("damping"), py::arg("res"), py::arg("median"));
+  m.def("trajectory", &trajectory,
+        "DPVO.terminate's interpolation (dpvo.py:385-417) -> [traj, root, info]",
+        py::arg("poses"), py::arg("tstamps"), py::arg("n"), py::arg("n_dev"),
+        py::arg("delta_log"), py::arg("delta_pairs"), py::arg("delta_count"), py::arg("counter"),
+        py::arg("inverse"));
   m.def("reproject_ordered_plan_insert", &ba_reproject_ordered_plan_insert,
         "reproject + edge order + BA plan + the new frame's pyramid insertion, one launch");
   m.def("reproject_ordered", &ba_reproject_ordered,

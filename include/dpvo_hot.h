@@ -566,6 +566,59 @@ int dpvo_edges_loop(const float* poses, const float* patches, const float* intri
                     int32_t* out_n, int32_t* errors, void* stream);
 size_t dpvo_edges_loop_work_floats(void);
 
+/* ---------------------------------------------------------------- front-end */
+
+/* The head of DPVO.__call__ (dpvo.py:931-965) in one launch of one workgroup,
+   no host synchronisation.  Frame row n = *n_dev when n_dev is non-null, else
+   the host n; frame counter likewise (int32 device scalars: graph-replayable).
+   times [times_cap] (fp64) holds the caller's frame times by frame counter
+   (the reference's tlist); times[counter] is written by the caller first.
+     tstamps[n]    = counter                                   (:933)
+     intrinsics[n] = new_intrinsics / res, fp32 division       (:934)
+     poses[n]      only when n > 1 (:943): motion_model 0 = poses[n-1] copied bit
+                   for bit (:956-957); 1 = Exp(damping fac Log(P1 P2^-1)) P1 with
+                   P1 = poses[n-1], P2 = poses[n-2], fac = (c - b) / (b - a) for
+                   a, b, c = times[counter-2 .. counter] (missing entries read
+                   as 1, :949); b == a gives fac = 1 (the reference raises).
+                   fp64 arithmetic, quaternions normalised on load, rounded to
+                   fp32 on store.
+     patches rows [n M, (n + 1) M) = new_patches [M, 3, P, P]; with median = 1
+                   and n >= 1 their channel 2 is the lower median (sorted rank
+                   (count - 1) / 2, what torch.median returns; NaN if any value
+                   is NaN) of channel 2 of the patches of frames [max(n-3, 0), n)
+                   (:962-965), by a four-pass radix select, not a sort.
+   Nothing else is written.  Host n outside [0, N), host counter outside
+   [0, times_cap), M / P / N <= 0 or a null pointer: DPVO_ERR_INVALID before any
+   launch; device values outside those ranges leave every buffer untouched.
+   3 M P P > 2^30: DPVO_ERR_UNSUPPORTED. */
+int dpvo_frame_init(float* poses, float* patches, float* intrinsics, int64_t* tstamps,
+                    const double* times, int times_cap, const float* new_patches,
+                    const float* new_intrinsics, int N, int M, int P, int n, const int32_t* n_dev,
+                    int counter, const int32_t* counter_dev, int motion_model, double damping,
+                    double res, int median, void* stream);
+
+/* DPVO.terminate's interpolation (dpvo.py:385-417): traj[t] = get_pose(t) for
+   t in [0, counter), or its inverse (inverse = 1, what terminate returns), from
+   poses [N, 7] / tstamps [N] of the n keyframes (n = *n_dev when non-null) and
+   the pg.delta log of dpvo_kf_shift: delta_log [cap, 7], delta_pairs [cap, 2] =
+   (t1, t0), *delta_count on the device.  Frame t is a keyframe when
+   tstamps[i] == t for some i < n (pose poses[i]; checked first, :386);
+   otherwise pose(t) = dP pose(t0) by the last record in log order with t1 == t,
+   through chains of any depth.  Records with t0 >= t1 or an index outside
+   [0, counter) are ignored.  A frame with neither, or whose chain ends at such
+   a frame, gets a NaN row.  root[t] = the row of `poses` frame t hangs on, -1
+   when unresolved; info = {unresolved frames, ignored records}.  fp64
+   arithmetic, unit quaternions, rounded to fp32 on store.
+   2 + ceil(log2(counter)) launches (table build, then pointer jumping; the
+   number depends on counter alone), no host synchronisation; counter == 0 is
+   a no-op.  workspace: dpvo_trajectory_workspace_bytes(counter). */
+size_t dpvo_trajectory_workspace_bytes(int counter);
+int dpvo_trajectory(const float* poses, const int64_t* tstamps, int N, int n, const int32_t* n_dev,
+                    const float* delta_log, const int64_t* delta_pairs,
+                    const int32_t* delta_count, int delta_cap, int counter, int inverse,
+                    float* traj, int64_t* root, int32_t* info, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------- update operator */
 
 /* DPVO's update operator, inference only (dpvo/net.py:175-339 `Update`, with
