@@ -11,28 +11,34 @@
 // load ~60-175 ns, dependent fp64 FMA 36 cycles, back-to-back launch 2.4 us.
 // A DPVO window is tiny (N <= 20 free poses, a few thousand edges), so one
 // CU runs out of latency hiding long before it runs out of FLOPs; the work
-// is spread over ~70 CUs and the launches are kept to 1 + iterations:
+// is spread over the CUs.  This file holds the multi-kernel solver (1 + 2 x
+// iterations + 1 launches), the small-graph path where the window solver
+// (ba_window.hip) declines:
 //
 //   ba_setup_kernel (1 workgroup, once per call): counting sort of the
 //       edges by patch in LDS (bitonic fallback for wide kk ranges) ->
 //       "positions" grouped by patch (edge, ii, jj, kk records), unique
 //       patches, per-patch free-pose masks and pose-block offsets.
-//   ba_iter_kernel (one launch per iteration, NL + ceil(E/512) workgroups):
-//     * one workgroup per lower 6x6 block (a, b) of S: every patch whose
-//       mask holds a and b is re-linearised by one thread (the fp32 edge
-//       math of the reference), which accumulates that patch's B, E Q E^T
-//       (and y) terms in fp64 registers; a fixed DPP tree + ordered
-//       cross-wave sum -> deterministic S block, no atomics;
-//     * patch-owner workgroups: Q_u, U_u and the E column blocks c_{u,p}
-//       of every patch (needed for dZ);
-//     * the last workgroup to arrive (one atomic ticket, agent-scope
-//       fences) damps S, runs the block Cholesky in LDS, the substitutions,
-//       the pose retraction and dZ + patch retraction.
+//   ba_lin_kernel (per iteration, thread per position): applies the previous
+//       iteration's depth step, then the fp32 edge math of the reference
+//       -> J and the E / C / u terms of every position.
+//   ba_schur_kernel (per iteration, one workgroup per lower 6x6 block (a, b)
+//       of S): sums the B, E Q E^T (and y) terms of every patch whose mask
+//       holds a and b in fp64; a fixed DPP tree + ordered cross-wave sum ->
+//       deterministic S block, no atomics.  Its last-arrival tail: the last
+//       workgroup to arrive (one atomic ticket, agent-scope fences) damps S,
+//       solves it by block Gauss-Jordan in LDS and retracts the poses.
+//   ba_solve_kernel: that tail as a launch of its own, from a given S, y.
+//   ba_apply_kernel (once, after the last iteration): writes the depths.
 //   The split (build_schur -> all-reduce(S,y) -> solve_update) launches the
 //   same code without / as the solve tail: the edge-sharded multi-GPU form
 //   (SURVEY 8e).
+//
+// Below the kernels: the C ABI of F-BA / F-REPROJ / F-NBR and the dispatch
+// between the three solvers (window, this one, large-graph: ba_paths.hpp).
 #include "common.hpp"
 #include "ba_device.hpp"  // bad::lin_edge: the one copy of the edge math
+#include "ba_paths.hpp"
 
 namespace dpvo {
 
@@ -44,8 +50,6 @@ constexpr int kMaxFree = 20;  // pose-block masks are 32-bit; lower S blocks of 
 constexpr int kPerThread = kMaxSetupE / kSetupThreads;
 constexpr int kCtlBytes = 512;
 constexpr int kSetupLds = 160 * 1024;
-constexpr int kMarks = 2432;  // [0, 128) phases; window kernel per workgroup: [128 + 256 it + g] assembled, [640 + 256 it + g] all partials seen, [1152 + g] setup, [1408 + g] it 0 pre-reduction; fused reproject + plan + insert launch: [1664 + 2b] / [1665 + 2b] start / end of workgroup b; window kernel [2176 + g] end of workgroup g
-constexpr int kLaunchMarks = 1664;
 constexpr int kNoPose = 31;
 constexpr int kEC = 16;  // doubles per position record of E terms
 
@@ -1026,53 +1030,23 @@ __global__ void __launch_bounds__(256)
     jx[e] = best_next;
   }
 }
-
-
-// ba_window.hip: plan kernel + persistent per-block workgroups, solve in every workgroup
-size_t ba_window_scratch_bytes(int E, int N);
-bool ba_window_supported(int E, int N, int P);
-int ba_window_launch(float* poses, float* patches, const float* intrinsics, const float* target,
-                     const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                     const int64_t* kk, int E, int P, int num_poses, int num_patches, int t0, int t1,
-                     int iterations, char* scratch, int* status, int64_t* marks, double* dxo,
-                     void* stream);
-int ba_window_plan(const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int num_patches,
-                   int num_poses, int t0, int t1, char* scratch, int* status, void* stream,
-                   const int* t0d);
-void ba_window_plan_offsets(int E, int64_t* out);
-int ba_window_reproject_plan(const float* poses, const float* patches, const float* intrinsics,
-                             const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int P,
-                             int num_poses, int num_patches, int N2, float* coords, int* order,
-                             int t0, int t1, char* scratch, int* status, void* stream,
-                             const int* t0d);
-int ba_window_reproject_plan_insert(const float* poses, const float* patches,
-                                    const float* intrinsics, const int64_t* ii, const int64_t* jj,
-                                    const int64_t* kk, int E, int P, int num_poses,
-                                    int num_patches, int N2, float* coords, int* order, int t0,
-                                    int t1, char* scratch, int* status, const void* src,
-                                    void* const* dst, const int* scale, int L, int C, int H, int W,
-                                    int half, int64_t* marks, void* stream);
-int ba_window_run(float* poses, float* patches, const float* intrinsics, const float* target,
-                  const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                  const int64_t* kk, int E, int P, int num_poses, int num_patches, int t0, int t1,
-                  int iterations, char* scratch, int* status, int64_t* marks, double* dxo,
-                  void* stream, const int* t0d);
-// ba_large.hip: large graphs (global BA, cfg4)
-size_t gba_workspace_bytes(int E, int N);
-int gba_forward(float* poses, float* patches, const float* intrinsics, const float* target,
-                const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                const int64_t* kk, int E, int P, int num_poses, int num_patches, int PPF, int t0,
-                int t1, int iterations, void* workspace, size_t workspace_bytes, void* stream);
-double* gba_dx(void* workspace, int E, int N);
-
 }  // namespace dpvo
 
+// ---------------------------------------------------------------------------
+// C ABI and the dispatch between the window solver (ba_window.hip), the
+// multi-kernel solver above and the large-graph solver (ba_large.hip).
+// ---------------------------------------------------------------------------
 namespace {
 // 0 auto (window), 2 multi-kernel, 4 large-graph path, 5 window (1 / 3 removed)
 int g_ba_path = 0;
 // instrumentation: phase marks stamped by the window kernel (dpvo_ba_set_marks)
 bool g_ba_marks = false;
+
+// multi-kernel path: OR the workspace status word into the caller's sticky word
+__global__ void k_status_or(const int* src, int* acc) {
+  if (threadIdx.x == 0) atomicOr(acc, *src);
 }
+}  // namespace
 
 using namespace dpvo;
 
@@ -1095,54 +1069,55 @@ static int pow2_at_least(int v) {
   return p;
 }
 
-static BaArgs make_args(float* poses, float* patches, const float* intrinsics, const float* target,
-                        const float* weight, const float* lmbda, const int64_t* ii,
-                        const int64_t* jj, const int64_t* kk, int E, int P, int num_poses,
-                        int num_patches, int t0, int t1) {
-  BaArgs a;
-  a.poses = poses;
-  a.patches = patches;
-  a.intrinsics = intrinsics;
-  a.target = target;
-  a.weight = weight;
-  a.lmbda = lmbda;
-  a.ii = ii;
-  a.jj = jj;
-  a.kk = kk;
-  a.E = E;
-  a.P = P;
-  a.num_poses = num_poses;
-  a.num_patches = num_patches;
-  a.t0 = t0;
-  a.N = t1 - t0;
-  return a;
+// the kernels' view of a problem: BaArgs keeps BaProblem's fields, in its order
+static BaArgs make_args(const BaProblem& p) {
+  return {p.poses, p.patches, p.intrinsics, p.target, p.weight, p.lmbda, p.ii, p.jj, p.kk,
+          p.E, p.P, p.num_poses, p.num_patches, p.t0, p.N};
 }
 
 static int schur_grid(int N) { return N * (N + 1) / 2; }
 static int lin_grid(int E) { return (E + 255) / 256; }
 
-// the window paths (blocks / fused / multi-kernel) cover E <= kMaxSetupE and
+// the small-graph paths (window / multi-kernel) cover E <= kMaxSetupE and
 // N <= kMaxFree; anything larger (global BA, cfg4) runs ba_large.hip
 static bool window_path_ok(int E, int N) { return E <= kMaxSetupE && N <= kMaxFree; }
 static bool use_large(int E, int N) { return g_ba_path == 4 || !window_path_ok(E, N); }
+// the selected mode lets dpvo_ba_forward take the window path where it is supported
+static bool window_selected() { return g_ba_path == 0 || g_ba_path == 5; }
 
 DPVO_EXPORT size_t dpvo_ba_workspace_bytes(int E, int t0, int t1) {
   const int N = t1 > t0 ? t1 - t0 : 0;
   const int Ep = E > 0 ? E : 1;
   size_t bytes = 0;
   if (window_path_ok(Ep, N)) {
-    size_t a = 0;
-    if (ba_window_supported(Ep, N, 3)) {
-      const size_t c = ba_window_scratch_bytes(Ep, N);
-      a = a > c ? a : c;
-    }
-    bytes = ba_layout(Ep, N, nullptr, nullptr) + a;
+    // the multi-kernel layout, then the window scratch where that path can run
+    bytes = ba_layout(Ep, N, nullptr, nullptr);
+    if (ba_window_supported(Ep, N, 3)) bytes += ba_window_scratch_bytes(Ep, N);
   }
   if (use_large(Ep, N)) {
     const size_t g = gba_workspace_bytes(Ep, N);
     bytes = g > bytes ? g : bytes;
   }
   return bytes;
+}
+
+// The window path's view of a workspace: its scratch lies behind the
+// multi-kernel layout, whose status word, marks and dX it borrows.
+static BaWindowWs window_ws(int E, int N, void* workspace) {
+  BaWs w;
+  const size_t base_bytes = ba_layout(E, N, (char*)workspace, &w);
+  return {(char*)workspace + base_bytes, w.meta + 1, g_ba_marks ? w.tmark : nullptr, w.dX};
+}
+
+// Admission of a call that only the window path serves: DPVO_ERR_UNSUPPORTED
+// where that path declines (E, N, P), else DPVO_ERR_WORKSPACE for a short
+// workspace, else DPVO_OK with *ws set.
+static int window_admit(int E, int N, int P, void* workspace, size_t workspace_bytes,
+                        BaWindowWs* ws) {
+  if (!ba_window_supported(E, N, P)) return DPVO_ERR_UNSUPPORTED;
+  if (workspace_bytes < dpvo_ba_workspace_bytes(E, 0, N)) return DPVO_ERR_WORKSPACE;
+  *ws = window_ws(E, N, workspace);
+  return DPVO_OK;
 }
 
 DPVO_EXPORT int dpvo_ba_select_path(int mode) {
@@ -1165,8 +1140,8 @@ DPVO_EXPORT int dpvo_ba_setup(const int64_t* ii, const int64_t* jj, const int64_
   BaWs w;
   ba_layout(E, N, (char*)workspace, &w);
   ensure_lds_limits();
-  BaArgs a = make_args(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ii, jj, kk, E, 0, 0,
-                       num_patches, t0, t1);
+  BaArgs a = make_args({nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ii, jj, kk, E, 0, 0,
+                        num_patches, t0, N, nullptr});
   hipLaunchKernelGGL(ba_setup_kernel, dim3(1), dim3(kSetupThreads), kSetupLds, as_stream(stream),
                      a, w, pow2_at_least(E < 2 ? 2 : E));
   return launch_status();
@@ -1185,8 +1160,8 @@ DPVO_EXPORT int dpvo_ba_build_schur(const float* poses, const float* patches,
   BaWs w;
   ba_layout(E, N, (char*)workspace, &w);
   ensure_lds_limits();
-  BaArgs a = make_args(const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, target,
-                       weight, lmbda, ii, jj, kk, E, P, num_poses, 0, t0, t1);
+  BaArgs a = make_args({const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, target,
+                        weight, lmbda, ii, jj, kk, E, P, num_poses, 0, t0, N, nullptr});
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(ba_lin_kernel, dim3(lin_grid(E)), dim3(256), 0, s, a, w, 0);
   int st = launch_status();
@@ -1208,8 +1183,8 @@ DPVO_EXPORT int dpvo_ba_solve_update(float* poses, float* patches, const double*
   ensure_lds_limits();
   // the patch retraction reads lmbda (Q = 1/(C + lmbda)) from the workspace
   // copy the build step made
-  BaArgs a = make_args(poses, patches, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, E, P, num_poses, 0, t0, t1);
+  BaArgs a = make_args({poses, patches, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, E, P, num_poses, 0, t0, N, nullptr});
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(kIterThreads), iter_lds(N), s, a, w,
                      S_lower ? S_lower : w.S, y ? y : w.y, dX_out);
@@ -1219,31 +1194,22 @@ DPVO_EXPORT int dpvo_ba_solve_update(float* poses, float* patches, const double*
   return launch_status();
 }
 
+// diagnostics read-out: workspace -> the caller's DEVICE array
+static int copy_out(void* out, const void* src, size_t bytes, void* stream) {
+  const hipError_t e = hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, as_stream(stream));
+  return e == hipSuccess ? DPVO_OK : DPVO_ERR_LAUNCH;
+}
+
 DPVO_EXPORT int dpvo_ba_last_status(const void* workspace, int E, int t0, int t1, int* out,
                                     void* stream) {
   if (!workspace || !out || E <= 0) return DPVO_ERR_INVALID;
   BaWs w;
   ba_layout(E, t1 > t0 ? t1 - t0 : 0, (char*)workspace, &w);
-  return hipMemcpyAsync(out, w.meta + 1, sizeof(int), hipMemcpyDeviceToDevice,
-                        as_stream(stream)) == hipSuccess
-             ? DPVO_OK
-             : DPVO_ERR_LAUNCH;
+  return copy_out(out, w.meta + 1, sizeof(int), stream);
 }
 
-namespace dpvo {
-int gba_status_or(const void* workspace, int E, int N, int* acc, void* stream);
-}
-namespace {
-__global__ void k_status_or(const int* src, int* acc) {
-  if (threadIdx.x == 0) atomicOr(acc, *src);
-}
-}  // namespace
-
-namespace dpvo {
-void ba_set_status_sink(int* sink);
-}
 DPVO_EXPORT int dpvo_ba_set_status_sink(int* acc) {
-  dpvo::ba_set_status_sink(acc);
+  ba_set_status_sink(acc);
   return DPVO_OK;
 }
 
@@ -1254,7 +1220,7 @@ DPVO_EXPORT int dpvo_ba_status_accumulate(const void* workspace, int E, int t0, 
   const int N = t1 > t0 ? t1 - t0 : 0;
   if (use_large(E, N)) return gba_status_or(workspace, E, N, acc, stream);
   // the window kernels OR their status into the registered sink themselves
-  if ((g_ba_path == 0 || g_ba_path == 5) && ba_window_supported(E, N, 3)) return DPVO_OK;
+  if (window_selected() && ba_window_supported(E, N, 3)) return DPVO_OK;
   BaWs w;
   ba_layout(E, N, (char*)workspace, &w);
   hipLaunchKernelGGL(k_status_or, dim3(1), dim3(64), 0, as_stream(stream), w.meta + 1, acc);
@@ -1266,10 +1232,7 @@ DPVO_EXPORT int dpvo_ba_phase_marks(const void* workspace, int E, int t0, int t1
   if (!workspace || !out || E <= 0) return DPVO_ERR_INVALID;
   BaWs w;
   ba_layout(E, t1 > t0 ? t1 - t0 : 0, (char*)workspace, &w);
-  return hipMemcpyAsync(out, w.tmark, sizeof(int64_t) * kMarks, hipMemcpyDeviceToDevice,
-                        as_stream(stream)) == hipSuccess
-             ? DPVO_OK
-             : DPVO_ERR_LAUNCH;
+  return copy_out(out, w.tmark, sizeof(int64_t) * kMarks, stream);
 }
 
 DPVO_EXPORT int dpvo_ba_set_marks(int on) {
@@ -1290,10 +1253,7 @@ DPVO_EXPORT int dpvo_ba_last_dx(const void* workspace, int E, int t0, int t1, do
     ba_layout(E, N, (char*)workspace, &w);
     src = w.dX;
   }
-  return hipMemcpyAsync(out, src, sizeof(double) * 6 * N, hipMemcpyDeviceToDevice,
-                        as_stream(stream)) == hipSuccess
-             ? DPVO_OK
-             : DPVO_ERR_LAUNCH;
+  return copy_out(out, src, sizeof(double) * 6 * N, stream);
 }
 
 // instrumentation: per-workgroup start/end stamps of the last iteration launch
@@ -1303,10 +1263,7 @@ DPVO_EXPORT int dpvo_ba_workgroup_marks(const void* workspace, int E, int t0, in
   const int N = t1 > t0 ? t1 - t0 : 0;
   BaWs w;
   ba_layout(E, N, (char*)workspace, &w);
-  return hipMemcpyAsync(out, w.wgt, sizeof(int64_t) * 2 * schur_grid(N),
-                        hipMemcpyDeviceToDevice, as_stream(stream)) == hipSuccess
-             ? DPVO_OK
-             : DPVO_ERR_LAUNCH;
+  return copy_out(out, w.wgt, sizeof(int64_t) * 2 * schur_grid(N), stream);
 }
 
 DPVO_EXPORT int dpvo_ba_forward(float* poses, float* patches, const float* intrinsics,
@@ -1323,21 +1280,16 @@ DPVO_EXPORT int dpvo_ba_forward(float* poses, float* patches, const float* intri
     return DPVO_ERR_INVALID;
   const int N = t1 - t0;
   if (workspace_bytes < dpvo_ba_workspace_bytes(E, t0, t1)) return DPVO_ERR_WORKSPACE;
-  if (use_large(E, N))
-    return gba_forward(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                       num_poses, num_patches, PPF, t0, t1, iterations, workspace,
-                       workspace_bytes, stream);
+  const BaProblem p = {poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
+                       num_poses, num_patches, t0, N, nullptr};
+  if (use_large(E, N)) return gba_forward(p, PPF, iterations, workspace, workspace_bytes, stream);
+  if (window_selected() && ba_window_supported(E, N, P))
+    return ba_window_launch(p, iterations, window_ws(E, N, workspace), stream);
   BaWs w;
-  const size_t base_bytes = ba_layout(E, N, (char*)workspace, &w);
-  if ((g_ba_path == 0 || g_ba_path == 5) && ba_window_supported(E, N, P))
-    return ba_window_launch(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                            num_poses, num_patches, t0, t1, iterations,
-                            (char*)workspace + base_bytes, w.meta + 1,
-                            g_ba_marks ? w.tmark : nullptr, w.dX, stream);
+  ba_layout(E, N, (char*)workspace, &w);
   ensure_lds_limits();
   hipStream_t s = as_stream(stream);
-  BaArgs a = make_args(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                       num_poses, num_patches, t0, t1);
+  BaArgs a = make_args(p);
   hipLaunchKernelGGL(ba_setup_kernel, dim3(1), dim3(kSetupThreads), kSetupLds, s, a, w,
                      pow2_at_least(E < 2 ? 2 : E));
   int st = launch_status();
@@ -1356,7 +1308,7 @@ DPVO_EXPORT int dpvo_ba_forward(float* poses, float* patches, const float* intri
 }
 
 DPVO_EXPORT int dpvo_ba_plan_supported(int E, int t0, int t1, int P) {
-  return (g_ba_path == 0 || g_ba_path == 5) && ba_window_supported(E, t1 - t0, P) ? 1 : 0;
+  return window_selected() && ba_window_supported(E, t1 - t0, P) ? 1 : 0;
 }
 
 DPVO_EXPORT int dpvo_ba_plan_offsets(int E, int t0, int t1, int64_t* out) {
@@ -1374,12 +1326,11 @@ DPVO_EXPORT int dpvo_ba_plan(const int64_t* ii, const int64_t* jj, const int64_t
   if (E <= 0) return DPVO_OK;
   if (!ii || !jj || !kk || !workspace || num_patches <= 0 || num_poses <= 0 || t1 < t0)
     return DPVO_ERR_INVALID;
-  if (!ba_window_supported(E, t1 - t0, 3)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, t0, t1)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, t1 - t0, (char*)workspace, &w);
-  return ba_window_plan(ii, jj, kk, E, num_patches, num_poses, t0, t1,
-                        (char*)workspace + base_bytes, w.meta + 1, stream, nullptr);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, t1 - t0, 3, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_plan({nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ii, jj, kk, E, 0,
+                         num_poses, num_patches, t0, t1 - t0, nullptr},
+                        ws, stream);
 }
 
 DPVO_EXPORT int dpvo_ba_forward_planned(float* poses, float* patches, const float* intrinsics,
@@ -1392,13 +1343,11 @@ DPVO_EXPORT int dpvo_ba_forward_planned(float* poses, float* patches, const floa
   if (P < 2 || num_poses <= 0 || num_patches <= 0 || t1 < t0 || !workspace || !poses ||
       !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk)
     return DPVO_ERR_INVALID;
-  if (!ba_window_supported(E, t1 - t0, P)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, t0, t1)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, t1 - t0, (char*)workspace, &w);
-  return ba_window_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                       num_poses, num_patches, t0, t1, iterations, (char*)workspace + base_bytes,
-                       w.meta + 1, g_ba_marks ? w.tmark : nullptr, w.dX, stream, nullptr);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, t1 - t0, P, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_run({poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
+                        num_poses, num_patches, t0, t1 - t0, nullptr},
+                       iterations, ws, stream);
 }
 
 DPVO_EXPORT int dpvo_ba_forward_planned_dev(float* poses, float* patches, const float* intrinsics,
@@ -1412,13 +1361,11 @@ DPVO_EXPORT int dpvo_ba_forward_planned_dev(float* poses, float* patches, const 
   if (P < 2 || num_poses <= 0 || num_patches <= 0 || N < 0 || !t0_dev || !workspace || !poses ||
       !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk)
     return DPVO_ERR_INVALID;
-  if (!ba_window_supported(E, N, P)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, 0, N)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, N, (char*)workspace, &w);
-  return ba_window_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                       num_poses, num_patches, 0, N, iterations, (char*)workspace + base_bytes,
-                       w.meta + 1, g_ba_marks ? w.tmark : nullptr, w.dX, stream, t0_dev);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, N, P, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_run({poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
+                        num_poses, num_patches, 0, N, t0_dev},
+                       iterations, ws, stream);
 }
 
 DPVO_EXPORT int dpvo_reproject(const float* poses, const float* patches, const float* intrinsics,
@@ -1448,6 +1395,8 @@ DPVO_EXPORT int dpvo_reproject_ordered(const float* poses, const float* patches,
   return launch_status();
 }
 
+// The fused start-of-update launches have no target / weight / lmbda and only
+// read poses / patches (the const_casts below).
 DPVO_EXPORT int dpvo_reproject_ordered_plan(const float* poses, const float* patches,
                                             const float* intrinsics, const int64_t* ii,
                                             const int64_t* jj, const int64_t* kk, int E, int P,
@@ -1458,13 +1407,12 @@ DPVO_EXPORT int dpvo_reproject_ordered_plan(const float* poses, const float* pat
   if (P <= 0 || num_poses <= 0 || num_patches <= 0 || !order || !coords || !poses || !patches ||
       !intrinsics || !ii || !jj || !kk || !workspace || t1 < t0)
     return DPVO_ERR_INVALID;
-  if (!ba_window_supported(E, t1 - t0, P)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, t0, t1)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, t1 - t0, (char*)workspace, &w);
-  return ba_window_reproject_plan(poses, patches, intrinsics, ii, jj, kk, E, P, num_poses,
-                                  num_patches, N2, coords, (int*)order, t0, t1,
-                                  (char*)workspace + base_bytes, w.meta + 1, stream, nullptr);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, t1 - t0, P, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_reproject_plan(
+      {const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, nullptr, nullptr,
+       nullptr, ii, jj, kk, E, P, num_poses, num_patches, t0, t1 - t0, nullptr},
+      N2, coords, (int*)order, ws, stream);
 }
 
 DPVO_EXPORT int dpvo_reproject_ordered_plan_insert(
@@ -1484,15 +1432,12 @@ DPVO_EXPORT int dpvo_reproject_ordered_plan_insert(
     if (scale[l] != 1 && scale[l] != 2 && scale[l] != 4 && scale[l] != 8)
       return DPVO_ERR_UNSUPPORTED;
   }
-  if (!ba_window_supported(E, t1 - t0, P)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, t0, t1)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, t1 - t0, (char*)workspace, &w);
-  return ba_window_reproject_plan_insert(poses, patches, intrinsics, ii, jj, kk, E, P, num_poses,
-                                         num_patches, N2, coords, (int*)order, t0, t1,
-                                         (char*)workspace + base_bytes, w.meta + 1, src, dst,
-                                         scale, L, C, H, W, dtype == DPVO_F16 ? 1 : 0,
-                                         g_ba_marks ? w.tmark + kLaunchMarks : nullptr, stream);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, t1 - t0, P, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_reproject_plan_insert(
+      {const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, nullptr, nullptr,
+       nullptr, ii, jj, kk, E, P, num_poses, num_patches, t0, t1 - t0, nullptr},
+      N2, coords, (int*)order, ws, src, dst, scale, L, C, H, W, dtype == DPVO_F16 ? 1 : 0, stream);
 }
 
 DPVO_EXPORT int dpvo_reproject_ordered_plan_dev(const float* poses, const float* patches,
@@ -1506,13 +1451,12 @@ DPVO_EXPORT int dpvo_reproject_ordered_plan_dev(const float* poses, const float*
   if (P <= 0 || num_poses <= 0 || num_patches <= 0 || !order || !coords || !poses || !patches ||
       !intrinsics || !ii || !jj || !kk || !workspace || !t0_dev || N < 0)
     return DPVO_ERR_INVALID;
-  if (!ba_window_supported(E, N, P)) return DPVO_ERR_UNSUPPORTED;
-  if (workspace_bytes < dpvo_ba_workspace_bytes(E, 0, N)) return DPVO_ERR_WORKSPACE;
-  BaWs w;
-  const size_t base_bytes = ba_layout(E, N, (char*)workspace, &w);
-  return ba_window_reproject_plan(poses, patches, intrinsics, ii, jj, kk, E, P, num_poses,
-                                  num_patches, N2, coords, (int*)order, 0, N,
-                                  (char*)workspace + base_bytes, w.meta + 1, stream, t0_dev);
+  BaWindowWs ws;
+  if (const int rc = window_admit(E, N, P, workspace, workspace_bytes, &ws)) return rc;
+  return ba_window_reproject_plan(
+      {const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, nullptr, nullptr,
+       nullptr, ii, jj, kk, E, P, num_poses, num_patches, 0, N, t0_dev},
+      N2, coords, (int*)order, ws, stream);
 }
 
 DPVO_EXPORT int dpvo_neighbors_max_edges(void) { return 1 << 30; }

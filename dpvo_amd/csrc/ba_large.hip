@@ -46,6 +46,7 @@
 
 #include "ba_bgj.hpp"
 #include "ba_device.hpp"
+#include "ba_paths.hpp"
 
 namespace dpvo {
 namespace gba {
@@ -1363,16 +1364,15 @@ double* gba_packed(void* workspace, int E, int N) {
   return w.packed;
 }
 
-int gba_forward(float* poses, float* patches, const float* intrinsics, const float* target,
-                const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                const int64_t* kk, int E, int P, int num_poses, int num_patches, int PPF, int t0,
-                int t1, int iterations, void* workspace, size_t workspace_bytes, void* stream) {
-  int st = gba_setup(ii, jj, kk, E, num_patches, PPF, t0, t1, 0, 0x7fffffff, workspace,
+int gba_forward(const BaProblem& p, int PPF, int iterations, void* workspace,
+                size_t workspace_bytes, void* stream) {
+  const int t0 = p.t0, t1 = p.t0 + p.N;
+  int st = gba_setup(p.ii, p.jj, p.kk, p.E, p.num_patches, PPF, t0, t1, 0, 0x7fffffff, workspace,
                      workspace_bytes, stream);
   for (int it = 0; it < iterations && st == DPVO_OK; it++) {
-    st = gba_build(poses, patches, intrinsics, target, weight, lmbda, ii, jj, E, P, num_poses, t0,
-                   t1, workspace, stream);
-    if (st == DPVO_OK) st = gba_solve_update(poses, patches, E, P, t0, t1, workspace, stream);
+    st = gba_build(p.poses, p.patches, p.intrinsics, p.target, p.weight, p.lmbda, p.ii, p.jj, p.E,
+                   p.P, p.num_poses, t0, t1, workspace, stream);
+    if (st == DPVO_OK) st = gba_solve_update(p.poses, p.patches, p.E, p.P, t0, t1, workspace, stream);
   }
   return st;
 }

@@ -41,6 +41,7 @@
 #include <map>
 #include <mutex>
 
+#include "ba_paths.hpp"
 #include "ba_solve.hpp"
 #include "pyr_insert.hpp"
 
@@ -115,11 +116,9 @@ struct WArgs {
   float* ejg;        // [2][E][12] E entries by edge and iteration parity (fp32), HBM fallback
   int* status;       // [1] OR of status bits (workspace meta)
   int* sink;         // caller's sticky status word (dpvo_ba_set_status_sink) or null
-  int64_t* marks;    // [2432] wall-clock stamps (instrumentation, dpvo_ba_set_marks): [0, 64)
-                     // phases of workgroup 0, [128 + 256 it + g] / [640 + 256 it + g] per
-                     // workgroup assembled / all partials seen, [1152 + g] setup done,
-                     // [1408 + g] iteration 0 assembled (before the reduction); null on
-                     // product calls
+  int64_t* marks;    // [kMarks] wall-clock stamps (instrumentation, dpvo_ba_set_marks; layout
+                     // in ba_paths.hpp): [0, 64) phases of workgroup 0, then per workgroup;
+                     // null on product calls
   double* dxo;       // [6N] dX of the latest iteration (workgroup 0; dpvo_ba_last_dx) or null
   const int* t0d;    // device t0 or null (then t0)
   unsigned long long salt;  // per-process random granule-key salt (see granule())
@@ -1712,7 +1711,7 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   }
   __syncthreads();
   mark(A, 1);
-  if (A.marks && tid == 0 && g < 256) A.marks[1152 + g] = (int64_t)wall_clock64();  // setup done
+  if (A.marks && tid == 0 && g < 256) A.marks[kMarkSetup + g] = (int64_t)wall_clock64();  // setup done
   const int nrel_e = nrel;
 
   // ---------------- iterations ----------------
@@ -1760,16 +1759,16 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
     } else if (diag) {
       assemble<1>(A, L, nrel_e, a, b, lam, fx, fy, cx, cy, it & 1, acc, nact);
       mark(A, mb + 4);
-      if (A.marks && tid == 0 && it == 0 && g < 256) A.marks[1408 + g] = (int64_t)wall_clock64();
+      if (A.marks && tid == 0 && it == 0 && g < 256) A.marks[kMarkPre + g] = (int64_t)wall_clock64();
       reduce_acc<27>(acc, red, gslot, gkey, nact);
     } else {
       assemble<2>(A, L, nrel_e, a, b, lam, fx, fy, cx, cy, it & 1, acc, nact);
-      if (A.marks && tid == 0 && it == 0 && g < 256) A.marks[1408 + g] = (int64_t)wall_clock64();
+      if (A.marks && tid == 0 && it == 0 && g < 256) A.marks[kMarkPre + g] = (int64_t)wall_clock64();
       reduce_acc<36>(acc, red, gslot, gkey, nact);
     }
     mark(A, mb + 0);
     if (A.marks && tid == 0 && it < 2 && g < 256)  // per-workgroup stamps (instrumentation)
-      A.marks[128 + 256 * it + g] = (int64_t)wall_clock64();
+      A.marks[kMarkAssembled + 256 * it + g] = (int64_t)wall_clock64();
     if (NB == 0) continue;  // structure only: dZ = Q u, applied after the loop
     const int NNb = N;
     double* Sd = reinterpret_cast<double*>(L.region);
@@ -1837,7 +1836,7 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
       if (late) ctl[cTimeout] = 1;
     }
     mark(A, mb + 1);
-    if (A.marks && tid == 0 && it < 2 && g < 256) A.marks[640 + 256 * it + g] = (int64_t)wall_clock64();
+    if (A.marks && tid == 0 && it < 2 && g < 256) A.marks[kMarkSeen + 256 * it + g] = (int64_t)wall_clock64();
     __syncthreads();
     mark(A, mb + 5);  // every thread's granules in LDS
     {
@@ -1999,7 +1998,7 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
       __hip_atomic_store(&A.flags[kEpochWord], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       mark(A, 63);
     }
-    if (A.marks && g < 256) A.marks[2176 + g] = (int64_t)wall_clock64();  // workgroup end
+    if (A.marks && g < 256) A.marks[kMarkEnd + g] = (int64_t)wall_clock64();  // workgroup end
   }
 }
 
@@ -2083,14 +2082,38 @@ bool ba_window_supported(int E, int N, int P) {
 }
 
 // granules of one grid: [2][G][kGranPad]
-static size_t gran_count(const WGrid& w) { return (size_t)2 * kGranPad * w.G; }
+static size_t gran_count(int G) { return (size_t)2 * kGranPad * G; }
+
+// The one layout of the window scratch, as byte offsets: the plan arrays
+// (Plan), which depend on E only, then the buffers of the iteration kernel for
+// a grid of G workgroups (callers that use the plan arrays alone pass G = 0).
+struct WScratch {
+  size_t epos, poff, pmask, pkk, meta;  // Plan
+  size_t part, gran, ejg;               // WArgs
+  size_t bytes;
+};
+static WScratch window_scratch(int E, int G) {
+  WScratch s;
+  size_t off = 0;
+  auto take = [&off](size_t bytes) {
+    const size_t at = off;
+    off += al256w(bytes);
+    return at;
+  };
+  s.epos = take(sizeof(int) * (size_t)E);
+  s.poff = take(sizeof(int) * (size_t)(E + 1));
+  s.pmask = take(sizeof(unsigned) * (size_t)E);
+  s.pkk = take(sizeof(int) * (size_t)E);
+  s.meta = take(kMetaBytes);  // nuniq, fmin, status; [16, 28): int64 phase stamps
+  s.part = take(sizeof(double) * 2 * kPartPad * (size_t)G);
+  s.gran = take((size_t)16 * gran_count(G));
+  s.ejg = take(sizeof(float) * 24 * (size_t)E);
+  s.bytes = off;
+  return s;
+}
 
 size_t ba_window_scratch_bytes(int E, int N) {
-  const WGrid w = window_grid(E, N);
-  return al256w(sizeof(int) * (size_t)E) + al256w(sizeof(int) * (size_t)(E + 1)) +
-         al256w(sizeof(unsigned) * (size_t)E) + al256w(sizeof(int) * (size_t)E) +
-         al256w(kMetaBytes) + al256w(sizeof(double) * 2 * kPartPad * (size_t)w.G) +
-         al256w((size_t)16 * gran_count(w)) + al256w(sizeof(float) * 24 * (size_t)E);
+  return window_scratch(E, window_grid(E, N).G).bytes;
 }
 
 namespace {
@@ -2131,30 +2154,49 @@ void ba_set_status_sink(int* sink) {
 
 // byte offsets of the plan arrays inside the window scratch (tests, tools)
 void ba_window_plan_offsets(int E, int64_t* out) {
-  out[0] = 0;                                                  // epos [E]
-  out[1] = out[0] + (int64_t)al256w(sizeof(int) * (size_t)E);  // poff [E + 1]
-  out[2] = out[1] + (int64_t)al256w(sizeof(int) * (size_t)(E + 1));  // pmask [E]
-  out[3] = out[2] + (int64_t)al256w(sizeof(unsigned) * (size_t)E);  // pkk [E]
-  out[4] = out[3] + (int64_t)al256w(sizeof(int) * (size_t)E);  // meta [8]: nuniq, fmin, status;
-                                                               // [16, 28): int64 phase stamps
+  const WScratch s = window_scratch(E, 0);
+  const size_t o[5] = {s.epos, s.poff, s.pmask, s.pkk, s.meta};
+  for (int k = 0; k < 5; k++) out[k] = (int64_t)o[k];
 }
 
-static Plan plan_view(char* scratch, int E, int* status) {
-  Plan p;
-  char* s = scratch;
-  p.epos = (int*)s;
-  s += al256w(sizeof(int) * (size_t)E);
-  p.poff = (int*)s;
-  s += al256w(sizeof(int) * (size_t)(E + 1));
-  p.pmask = (unsigned*)s;
-  s += al256w(sizeof(unsigned) * (size_t)E);
-  p.pkk = (int*)s;
-  s += al256w(sizeof(int) * (size_t)E);
-  p.meta = (int*)s;
-  p.status = status;
-  p.sink = sink_for_device();
-  p.t0d = nullptr;
-  return p;
+static Plan plan_view(const BaProblem& p, const BaWindowWs& ws) {
+  const WScratch s = window_scratch(p.E, 0);
+  Plan v;
+  v.epos = (int*)(ws.scratch + s.epos);
+  v.poff = (int*)(ws.scratch + s.poff);
+  v.pmask = (unsigned*)(ws.scratch + s.pmask);
+  v.pkk = (int*)(ws.scratch + s.pkk);
+  v.meta = (int*)(ws.scratch + s.meta);
+  v.status = ws.status;
+  v.sink = sink_for_device();
+  v.t0d = p.t0d;
+  return v;
+}
+
+// the launch arguments the two fused start-of-update launches share; the
+// caller sets `spread` once it knows its grid
+static RArgs reproject_args(const BaProblem& p, int N2, float* coords, int* order,
+                            int64_t* marks) {
+  RArgs r;
+  r.marks = marks;
+  r.poses = p.poses;
+  r.patches = p.patches;
+  r.intrinsics = p.intrinsics;
+  r.ii = p.ii;
+  r.jj = p.jj;
+  r.kk = p.kk;
+  r.E = p.E;
+  r.P = p.P;
+  r.num_poses = p.num_poses;
+  r.num_patches = p.num_patches;
+  r.N2 = N2;
+  r.t0 = p.t0;
+  r.N = p.N;
+  r.coords = coords;
+  r.order = order;
+  r.nps = plan_shards(p.E);
+  r.spread = 0;
+  return r;
 }
 
 static void set_attrs() {
@@ -2176,82 +2218,37 @@ static void set_attrs() {
 
 // edge grouping only (reads ii / jj / kk): may run on another stream than
 // the iterations, e.g. concurrently with A-CORR
-int ba_window_plan(const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int num_patches,
-                   int num_poses, int t0, int t1, char* scratch, int* status, void* stream,
-                   const int* t0d) {
+int ba_window_plan(const BaProblem& p, const BaWindowWs& ws, void* stream) {
   set_attrs();
-  Plan plan = plan_view(scratch, E, status);
-  plan.t0d = t0d;
-  hipLaunchKernelGGL(ba_plan_kernel, dim3(plan_shards(E)), dim3(kPT), kWLds, as_stream(stream), ii, jj, kk, E,
-                     num_patches, num_poses, t0, t1 - t0, plan);
+  hipLaunchKernelGGL(ba_plan_kernel, dim3(plan_shards(p.E)), dim3(kPT), kWLds, as_stream(stream),
+                     p.ii, p.jj, p.kk, p.E, p.num_patches, p.num_poses, p.t0, p.N,
+                     plan_view(p, ws));
   return launch_status();
 }
 
 // reprojection + A-CORR edge order + edge grouping in one launch (shapes
 // validated by the caller, dpvo_reproject_ordered_plan)
-int ba_window_reproject_plan(const float* poses, const float* patches, const float* intrinsics,
-                             const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int P,
-                             int num_poses, int num_patches, int N2, float* coords, int* order,
-                             int t0, int t1, char* scratch, int* status, void* stream,
-                             const int* t0d) {
+int ba_window_reproject_plan(const BaProblem& p, int N2, float* coords, int* order,
+                             const BaWindowWs& ws, void* stream) {
   set_attrs();
-  Plan plan = plan_view(scratch, E, status);
-  plan.t0d = t0d;
-  RArgs r;
-  r.marks = nullptr;
-  r.poses = poses;
-  r.patches = patches;
-  r.intrinsics = intrinsics;
-  r.ii = ii;
-  r.jj = jj;
-  r.kk = kk;
-  r.E = E;
-  r.P = P;
-  r.num_poses = num_poses;
-  r.num_patches = num_patches;
-  r.N2 = N2;
-  r.t0 = t0;
-  r.N = t1 - t0;
-  r.coords = coords;
-  r.order = order;
-  r.nps = plan_shards(E);
-  const int total = E * P * P, grid = r.nps + 1 + (total + kPT - 1) / kPT;
+  RArgs r = reproject_args(p, N2, coords, order, nullptr);
+  const int total = p.E * p.P * p.P, grid = r.nps + 1 + (total + kPT - 1) / kPT;
   r.spread = launch_spread(r.nps, grid);
   hipLaunchKernelGGL(reproject_plan_kernel, dim3(grid), dim3(kPT), kWLds, as_stream(stream), r,
-                     plan);
+                     plan_view(p, ws));
   return launch_status();
 }
 
 // reproject + order + plan + frame insertion (src [C, H, W] NCHW fp32 / fp16,
 // dst[l] the channels-last slot of level l, scale[l] in {1, 2, 4, 8})
-int ba_window_reproject_plan_insert(const float* poses, const float* patches,
-                                    const float* intrinsics, const int64_t* ii, const int64_t* jj,
-                                    const int64_t* kk, int E, int P, int num_poses,
-                                    int num_patches, int N2, float* coords, int* order, int t0,
-                                    int t1, char* scratch, int* status, const void* src,
-                                    void* const* dst, const int* scale, int L, int C, int H, int W,
-                                    int half, int64_t* marks, void* stream) {
+int ba_window_reproject_plan_insert(const BaProblem& p, int N2, float* coords, int* order,
+                                    const BaWindowWs& ws, const void* src, void* const* dst,
+                                    const int* scale, int L, int C, int H, int W, int half,
+                                    void* stream) {
   set_attrs();
-  Plan plan = plan_view(scratch, E, status);
-  plan.t0d = nullptr;
-  RArgs r;
-  r.marks = marks;
-  r.poses = poses;
-  r.patches = patches;
-  r.intrinsics = intrinsics;
-  r.ii = ii;
-  r.jj = jj;
-  r.kk = kk;
-  r.E = E;
-  r.P = P;
-  r.num_poses = num_poses;
-  r.num_patches = num_patches;
-  r.N2 = N2;
-  r.t0 = t0;
-  r.N = t1 - t0;
-  r.coords = coords;
-  r.order = order;
-  r.nps = plan_shards(E);
+  const Plan plan = plan_view(p, ws);
+  const int E = p.E, P = p.P;
+  RArgs r = reproject_args(p, N2, coords, order, ws.marks ? ws.marks + kLaunchMarks : nullptr);
   InsArgs I = {};
   I.src = src;
   I.L = L;
@@ -2283,72 +2280,50 @@ int ba_window_reproject_plan_insert(const float* poses, const float* patches,
   return launch_status();
 }
 
-int ba_window_run(float* poses, float* patches, const float* intrinsics, const float* target,
-                  const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                  const int64_t* kk, int E, int P, int num_poses, int num_patches, int t0, int t1,
-                  int iterations, char* scratch, int* status, int64_t* marks, double* dxo,
-                  void* stream, const int* t0d = nullptr);
-
-int ba_window_launch(float* poses, float* patches, const float* intrinsics, const float* target,
-                     const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                     const int64_t* kk, int E, int P, int num_poses, int num_patches, int t0, int t1,
-                     int iterations, char* scratch, int* status, int64_t* marks, double* dxo,
-                     void* stream) {
-  const int rc = ba_window_plan(ii, jj, kk, E, num_patches, num_poses, t0, t1, scratch, status,
-                                stream, nullptr);
+int ba_window_launch(const BaProblem& p, int iterations, const BaWindowWs& ws, void* stream) {
+  const int rc = ba_window_plan(p, ws, stream);
   if (rc) return rc;
-  return ba_window_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P,
-                       num_poses, num_patches, t0, t1, iterations, scratch, status, marks, dxo,
-                       stream);
+  return ba_window_run(p, iterations, ws, stream);
 }
 
-int ba_window_run(float* poses, float* patches, const float* intrinsics, const float* target,
-                  const float* weight, const float* lmbda, const int64_t* ii, const int64_t* jj,
-                  const int64_t* kk, int E, int P, int num_poses, int num_patches, int t0, int t1,
-                  int iterations, char* scratch, int* status, int64_t* marks, double* dxo,
-                  void* stream, const int* t0d) {
+int ba_window_run(const BaProblem& p, int iterations, const BaWindowWs& ws, void* stream) {
   set_attrs();
   if (iterations > 63) return DPVO_ERR_UNSUPPORTED;  // 6-bit iteration tag per epoch
-  const int N = t1 - t0;
-  const WGrid w = window_grid(E, N);
+  const WGrid w = window_grid(p.E, p.N);
+  const WScratch s = window_scratch(p.E, w.G);
   hipStream_t st = as_stream(stream);
   WArgs a;
   a.flags = wflag_slot(st);
   if (!a.flags) return DPVO_ERR_LAUNCH;
-  a.plan = plan_view(scratch, E, status);
-  char* s = scratch + al256w(sizeof(int) * (size_t)E) + al256w(sizeof(int) * (size_t)(E + 1)) +
-            al256w(sizeof(unsigned) * (size_t)E) + al256w(sizeof(int) * (size_t)E) +
-            al256w(kMetaBytes);
-  a.part = (double*)s;
-  s += al256w(sizeof(double) * 2 * kPartPad * (size_t)w.G);
-  a.gran = (v4u*)s;
-  s += al256w((size_t)16 * gran_count(w));
-  a.ejg = (float*)s;
-  a.poses = poses;
-  a.patches = patches;
-  a.intrinsics = intrinsics;
-  a.target = target;
-  a.weight = weight;
-  a.lmbda = lmbda;
-  a.ii = ii;
-  a.jj = jj;
-  a.kk = kk;
-  a.E = E;
-  a.P = P;
-  a.num_poses = num_poses;
-  a.num_patches = num_patches;
-  a.t0 = t0;
-  a.t0d = t0d;
-  a.N = N;
+  a.plan = plan_view(p, ws);
+  a.part = (double*)(ws.scratch + s.part);
+  a.gran = (v4u*)(ws.scratch + s.gran);
+  a.ejg = (float*)(ws.scratch + s.ejg);
+  a.poses = p.poses;
+  a.patches = p.patches;
+  a.intrinsics = p.intrinsics;
+  a.target = p.target;
+  a.weight = p.weight;
+  a.lmbda = p.lmbda;
+  a.ii = p.ii;
+  a.jj = p.jj;
+  a.kk = p.kk;
+  a.E = p.E;
+  a.P = p.P;
+  a.num_poses = p.num_poses;
+  a.num_patches = p.num_patches;
+  a.t0 = p.t0;
+  a.t0d = p.t0d;
+  a.N = p.N;
   a.iters = iterations;
   a.NB = w.NB;
   a.Sd = w.Sd;
   a.So = w.So;
   a.G = w.G;
-  a.status = status;
+  a.status = ws.status;
   a.sink = a.plan.sink;
-  a.marks = marks;
-  a.dxo = dxo;
+  a.marks = ws.marks;
+  a.dxo = ws.dxo;
   a.salt = granule_salt();
   hipLaunchKernelGGL(ba_window_kernel, dim3(w.G), dim3(kWT), kWLds, st, a);
   return launch_status();

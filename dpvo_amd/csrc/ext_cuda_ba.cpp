@@ -134,12 +134,60 @@ int ba_check_status(torch::Tensor like) {
   return all;
 }
 
-// ba.cpp:32-45 -> cuda_ba (ba_cuda.cu:433-582).  Mutates poses / patches.
-static torch::Tensor ba_forward_ws(torch::Tensor poses, torch::Tensor patches,
-                                      torch::Tensor intrinsics, torch::Tensor target,
-                                      torch::Tensor weight, torch::Tensor lmbda, torch::Tensor ii,
-                                      torch::Tensor jj, torch::Tensor kk, int PPF, int t0, int t1,
-                                      int iterations, bool eff_impl) {
+// ---------------------------------------------------------------------------
+// Input validation shared by the BA and reprojection entries.  Both helpers
+// normalise the caller's tensors in place (which keeps their storage alive)
+// and hand back raw pointers; a tensor that is already contiguous is kept as
+// it is: no copy, no allocation, no device query.
+// ---------------------------------------------------------------------------
+struct EdgeIn {
+  float* poses;
+  float* patches;
+  const float* intrinsics;
+  const int64_t* ii;
+  const int64_t* jj;
+  const int64_t* kk;
+  int P, E, num_poses, num_patches;
+};
+
+// The edge inputs of every entry: GPU tensors, float32 / int64, made
+// contiguous, ii / jj / kk of one length (the kernels read jj[e] and kk[e] for
+// every e < ii.numel()).  Non-contiguous poses / patches are copied, which
+// suits the reprojections; the in-place entries call ba_inputs first.
+static EdgeIn edge_inputs(torch::Tensor& poses, torch::Tensor& patches, torch::Tensor& intrinsics,
+                          torch::Tensor& ii, torch::Tensor& jj, torch::Tensor& kk) {
+  poses = f32_contig(poses, "poses");
+  patches = f32_contig(patches, "patches");
+  intrinsics = f32_contig(intrinsics, "intrinsics");
+  ii = idx64(ii, "ii");
+  jj = idx64(jj, "jj");
+  kk = idx64(kk, "kk");
+  EdgeIn e;
+  e.P = patches.size(-1);
+  e.E = ii.numel();
+  TORCH_CHECK(jj.numel() == e.E && kk.numel() == e.E, "ii, jj, kk must have equal length");
+  e.num_poses = poses.numel() / 7;
+  e.num_patches = patches.numel() / (3 * e.P * e.P);
+  e.poses = poses.data_ptr<float>();
+  e.patches = patches.data_ptr<float>();
+  e.intrinsics = intrinsics.data_ptr<float>();
+  e.ii = ii.data_ptr<int64_t>();
+  e.jj = jj.data_ptr<int64_t>();
+  e.kk = kk.data_ptr<int64_t>();
+  return e;
+}
+
+struct BaIn {
+  const float* target;
+  const float* weight;
+  const float* lmbda;
+};
+
+// What the in-place BA entries need beyond the edges: poses / patches that the
+// kernels can update where they are, and the residual inputs.  The sizes of
+// target / weight against E stay with each entry.
+static BaIn ba_inputs(const torch::Tensor& poses, const torch::Tensor& patches,
+                      torch::Tensor& target, torch::Tensor& weight, torch::Tensor& lmbda) {
   check_device(poses, "poses");
   check_device(patches, "patches");
   TORCH_CHECK(poses.scalar_type() == torch::kFloat32 && patches.scalar_type() == torch::kFloat32,
@@ -148,35 +196,35 @@ static torch::Tensor ba_forward_ws(torch::Tensor poses, torch::Tensor patches,
   // storage for the in-place update to land (ba_cuda.cu:458-459)
   TORCH_CHECK(poses.is_contiguous() && patches.is_contiguous(),
               "poses and patches must be contiguous (updated in place)");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  const int P = patches.size(-1);
-  const int num_poses = poses.numel() / 7;
-  const int num_patches = patches.numel() / (3 * P * P);
-  intrinsics = f32_contig(intrinsics, "intrinsics");
   target = f32_contig(target, "target");
   weight = f32_contig(weight, "weight");
   lmbda = f32_contig(lmbda, "lmbda");
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int E = ii.numel();
-  TORCH_CHECK(jj.numel() == E && kk.numel() == E, "ii, jj, kk must have equal length");
-  TORCH_CHECK(target.numel() >= 2 * E && weight.numel() >= 2 * E, "target/weight must be [.., E, 2]");
-  if (E == 0 || iterations <= 0) return torch::Tensor();
+  return {target.data_ptr<float>(), weight.data_ptr<float>(), lmbda.data_ptr<float>()};
+}
+
+// ba.cpp:32-45 -> cuda_ba (ba_cuda.cu:433-582).  Mutates poses / patches.
+static torch::Tensor ba_forward_ws(torch::Tensor poses, torch::Tensor patches,
+                                      torch::Tensor intrinsics, torch::Tensor target,
+                                      torch::Tensor weight, torch::Tensor lmbda, torch::Tensor ii,
+                                      torch::Tensor jj, torch::Tensor kk, int PPF, int t0, int t1,
+                                      int iterations, bool eff_impl) {
+  const BaIn b = ba_inputs(poses, patches, target, weight, lmbda);
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  TORCH_CHECK(target.numel() >= 2 * e.E && weight.numel() >= 2 * e.E,
+              "target/weight must be [.., E, 2]");
+  if (e.E == 0 || iterations <= 0) return torch::Tensor();
   TORCH_CHECK(t1 - t0 <= dpvo_ba_max_free_poses(), "cuda_ba.forward: t1 - t0 = ", t1 - t0,
               " free poses exceeds this build's limit (", dpvo_ba_max_free_poses(), ")");
   poll_status(poses);  // a previous call's fatal status raises here
-  const size_t wsb = dpvo_ba_workspace_bytes(E, t0, t1);
+  const size_t wsb = dpvo_ba_workspace_bytes(e.E, t0, t1);
   auto ws = torch::empty({(int64_t)wsb}, poses.options().dtype(torch::kUInt8));
-  check_status(dpvo_ba_forward(poses.data_ptr<float>(), patches.data_ptr<float>(),
-                               intrinsics.data_ptr<float>(), target.data_ptr<float>(),
-                               weight.data_ptr<float>(), lmbda.data_ptr<float>(),
-                               ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(),
-                               kk.data_ptr<int64_t>(), E, P, num_poses, num_patches, PPF, t0, t1,
+  check_status(dpvo_ba_forward(e.poses, e.patches, e.intrinsics, b.target, b.weight, b.lmbda, e.ii,
+                               e.jj, e.kk, e.E, e.P, e.num_poses, e.num_patches, PPF, t0, t1,
                                iterations, eff_impl ? 1 : 0, ws.data_ptr(), wsb,
                                current_stream()),
                "cuda_ba.forward");
-  track_status(ws, poses, E, t0, t1);
+  track_status(ws, poses, e.E, t0, t1);
   return ws;
 }
 
@@ -222,38 +270,22 @@ void ba_forward_planned(torch::Tensor ws, torch::Tensor poses, torch::Tensor pat
                         torch::Tensor intrinsics, torch::Tensor target, torch::Tensor weight,
                         torch::Tensor lmbda, torch::Tensor ii, torch::Tensor jj, torch::Tensor kk,
                         int t0, int t1, int iterations) {
-  check_device(poses, "poses");
-  check_device(patches, "patches");
-  TORCH_CHECK(poses.scalar_type() == torch::kFloat32 && patches.scalar_type() == torch::kFloat32,
-              "poses / patches must be float32");
-  TORCH_CHECK(poses.is_contiguous() && patches.is_contiguous(),
-              "poses and patches must be contiguous (updated in place)");
+  const BaIn b = ba_inputs(poses, patches, target, weight, lmbda);
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  const int P = patches.size(-1);
-  const int num_poses = poses.numel() / 7;
-  const int num_patches = patches.numel() / (3 * P * P);
-  intrinsics = f32_contig(intrinsics, "intrinsics");
-  target = f32_contig(target, "target");
-  weight = f32_contig(weight, "weight");
-  lmbda = f32_contig(lmbda, "lmbda");
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int E = ii.numel();
-  TORCH_CHECK(target.numel() >= 2 * E && weight.numel() >= 2 * E, "target/weight must be [.., E, 2]");
-  if (E == 0 || iterations <= 0) return;
+  TORCH_CHECK(target.numel() >= 2 * e.E && weight.numel() >= 2 * e.E,
+              "target/weight must be [.., E, 2]");
+  if (e.E == 0 || iterations <= 0) return;
   poll_status(poses);
-  check_status(dpvo_ba_forward_planned(poses.data_ptr<float>(), patches.data_ptr<float>(),
-                                       intrinsics.data_ptr<float>(), target.data_ptr<float>(),
-                                       weight.data_ptr<float>(), lmbda.data_ptr<float>(),
-                                       ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(),
-                                       kk.data_ptr<int64_t>(), E, P, num_poses, num_patches, t0,
-                                       t1, iterations, ws.data_ptr(), ws.numel(), current_stream()),
+  check_status(dpvo_ba_forward_planned(e.poses, e.patches, e.intrinsics, b.target, b.weight,
+                                       b.lmbda, e.ii, e.jj, e.kk, e.E, e.P, e.num_poses,
+                                       e.num_patches, t0, t1, iterations, ws.data_ptr(),
+                                       ws.numel(), current_stream()),
                "cuda_ba.forward_planned");
-  track_status(ws, poses, E, t0, t1);
+  track_status(ws, poses, e.E, t0, t1);
 }
 
-// Same call; returns the 2432 phase marks (100 MHz ticks: [0, 128) phases; window kernel
+// Same call; returns the DPVO_BA_MARKS phase marks (100 MHz ticks: [0, 128) phases; window kernel
 // [128 + 256 it + g] / [640 + 256 it + g] per-workgroup assembled / partials seen, [1152 + g]
 // setup done, [1408 + g] iteration 0 assembled before its reduction) followed by the
 // multi-kernel path's per-workgroup marks.
@@ -272,7 +304,7 @@ torch::Tensor ba_forward_marks(torch::Tensor poses, torch::Tensor patches,
     throw;
   }
   check_status(dpvo_ba_set_marks(0), "cuda_ba.forward_marks");
-  auto out = torch::zeros({2432}, poses.options().dtype(torch::kInt64));
+  auto out = torch::zeros({DPVO_BA_MARKS}, poses.options().dtype(torch::kInt64));
   if (!ws.defined()) return out;
   check_status(dpvo_ba_phase_marks(ws.data_ptr(), ii.numel(), t0, t1, out.data_ptr<int64_t>(),
                                    current_stream()),
@@ -292,7 +324,7 @@ torch::Tensor ba_workspace_marks(torch::Tensor ws, int64_t E, int t0, int t1) {
   TORCH_CHECK(E >= 0 && t1 > t0, "cuda_ba.workspace_marks: bad E / window");
   TORCH_CHECK((size_t)ws.nbytes() >= dpvo_ba_workspace_bytes((int)E, t0, t1),
               "cuda_ba.workspace_marks: ws is not a BA workspace planned for (E, t0, t1)");
-  auto out = torch::zeros({2432}, ws.options().dtype(torch::kInt64));
+  auto out = torch::zeros({DPVO_BA_MARKS}, ws.options().dtype(torch::kInt64));
   check_status(dpvo_ba_phase_marks(ws.data_ptr(), (int)E, t0, t1, out.data_ptr<int64_t>(),
                                    current_stream()),
                "cuda_ba.workspace_marks");
@@ -330,48 +362,29 @@ torch::Tensor ba_last_dx(torch::Tensor ws, int64_t E, int t0, int t1) {
 // ba.cpp:47-53 -> cuda_reproject (ba_cuda.cu:585-616)
 torch::Tensor ba_reproject(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics,
                            torch::Tensor ii, torch::Tensor jj, torch::Tensor kk) {
-  poses = f32_contig(poses, "poses");
-  patches = f32_contig(patches, "patches");
-  intrinsics = f32_contig(intrinsics, "intrinsics");
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int P = patches.size(-1);
-  const int E = ii.numel();
-  auto coords = torch::empty({E, 2, P, P}, poses.options());
-  check_status(dpvo_reproject(poses.data_ptr<float>(), patches.data_ptr<float>(),
-                              intrinsics.data_ptr<float>(), ii.data_ptr<int64_t>(),
-                              jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                              poses.numel() / 7, patches.numel() / (3 * P * P),
-                              coords.data_ptr<float>(), current_stream()),
+  auto coords = torch::empty({e.E, 2, e.P, e.P}, poses.options());
+  check_status(dpvo_reproject(e.poses, e.patches, e.intrinsics, e.ii, e.jj, e.kk, e.E, e.P,
+                              e.num_poses, e.num_patches, coords.data_ptr<float>(),
+                              current_stream()),
                "cuda_ba.reproject");
-  return coords.view({1, E, 2, P, P});
+  return coords.view({1, e.E, 2, e.P, e.P});
 }
 
 // reproject + the A-CORR edge order (edges grouped by target frame) in one launch
 std::vector<torch::Tensor> ba_reproject_ordered(torch::Tensor poses, torch::Tensor patches,
                                                 torch::Tensor intrinsics, torch::Tensor ii,
                                                 torch::Tensor jj, torch::Tensor kk, int N2) {
-  poses = f32_contig(poses, "poses");
-  patches = f32_contig(patches, "patches");
-  intrinsics = f32_contig(intrinsics, "intrinsics");
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int P = patches.size(-1);
-  const int E = ii.numel();
-  auto coords = torch::empty({E, 2, P, P}, poses.options());
-  auto order = torch::empty({E}, poses.options().dtype(torch::kInt32));
-  check_status(dpvo_reproject_ordered(poses.data_ptr<float>(), patches.data_ptr<float>(),
-                                      intrinsics.data_ptr<float>(), ii.data_ptr<int64_t>(),
-                                      jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                                      poses.numel() / 7, patches.numel() / (3 * P * P), N2,
-                                      coords.data_ptr<float>(), order.data_ptr<int32_t>(),
-                                      current_stream()),
+  auto coords = torch::empty({e.E, 2, e.P, e.P}, poses.options());
+  auto order = torch::empty({e.E}, poses.options().dtype(torch::kInt32));
+  check_status(dpvo_reproject_ordered(e.poses, e.patches, e.intrinsics, e.ii, e.jj, e.kk, e.E, e.P,
+                                      e.num_poses, e.num_patches, N2, coords.data_ptr<float>(),
+                                      order.data_ptr<int32_t>(), current_stream()),
                "cuda_ba.reproject_ordered");
-  return {coords.view({1, E, 2, P, P}), order};
+  return {coords.view({1, e.E, 2, e.P, e.P}), order};
 }
 
 // reproject + edge order + BA plan (workspace for forward_planned) in one launch
@@ -379,27 +392,18 @@ std::vector<torch::Tensor> ba_reproject_ordered_plan(torch::Tensor poses, torch:
                                                      torch::Tensor intrinsics, torch::Tensor ii,
                                                      torch::Tensor jj, torch::Tensor kk, int N2,
                                                      int t0, int t1) {
-  poses = f32_contig(poses, "poses");
-  patches = f32_contig(patches, "patches");
-  intrinsics = f32_contig(intrinsics, "intrinsics");
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int P = patches.size(-1);
-  const int E = ii.numel();
-  TORCH_CHECK(jj.numel() == E && kk.numel() == E, "ii, jj, kk must have equal length");
-  auto coords = torch::empty({E, 2, P, P}, poses.options());
-  auto order = torch::empty({E}, poses.options().dtype(torch::kInt32));
-  const size_t wsb = dpvo_ba_workspace_bytes(E, t0, t1);
+  auto coords = torch::empty({e.E, 2, e.P, e.P}, poses.options());
+  auto order = torch::empty({e.E}, poses.options().dtype(torch::kInt32));
+  const size_t wsb = dpvo_ba_workspace_bytes(e.E, t0, t1);
   auto ws = torch::empty({(int64_t)wsb}, poses.options().dtype(torch::kUInt8));
-  check_status(dpvo_reproject_ordered_plan(
-                   poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(),
-                   ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                   poses.numel() / 7, patches.numel() / (3 * P * P), N2, coords.data_ptr<float>(),
-                   order.data_ptr<int32_t>(), t0, t1, ws.data_ptr(), wsb, current_stream()),
+  check_status(dpvo_reproject_ordered_plan(e.poses, e.patches, e.intrinsics, e.ii, e.jj, e.kk, e.E,
+                                           e.P, e.num_poses, e.num_patches, N2,
+                                           coords.data_ptr<float>(), order.data_ptr<int32_t>(), t0,
+                                           t1, ws.data_ptr(), wsb, current_stream()),
                "cuda_ba.reproject_ordered_plan");
-  return {coords.view({1, E, 2, P, P}), order, ws};
+  return {coords.view({1, e.E, 2, e.P, e.P}), order, ws};
 }
 
 // ... plus the new frame's pyramid insertion in the same launch (src [C, H, W]
@@ -408,13 +412,8 @@ std::vector<torch::Tensor> ba_reproject_ordered_plan_insert(
     torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics, torch::Tensor ii,
     torch::Tensor jj, torch::Tensor kk, int N2, int t0, int t1, torch::Tensor src,
     std::vector<torch::Tensor> dst, std::vector<int64_t> scales) {
-  poses = f32_contig(poses, "poses");
-  patches = f32_contig(patches, "patches");
-  intrinsics = f32_contig(intrinsics, "intrinsics");
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
   check_device(src, "src");
   TORCH_CHECK(src.dim() == 3, "src must be [C, H, W]");
   TORCH_CHECK(src.scalar_type() == torch::kFloat32 || src.scalar_type() == torch::kFloat16,
@@ -436,22 +435,17 @@ std::vector<torch::Tensor> ba_reproject_ordered_plan_insert(
     ptrs.push_back(d.data_ptr());
     sc.push_back(s);
   }
-  const int P = patches.size(-1);
-  const int E = ii.numel();
-  TORCH_CHECK(jj.numel() == E && kk.numel() == E, "ii, jj, kk must have equal length");
-  auto coords = torch::empty({E, 2, P, P}, poses.options());
-  auto order = torch::empty({E}, poses.options().dtype(torch::kInt32));
-  const size_t wsb = dpvo_ba_workspace_bytes(E, t0, t1);
+  auto coords = torch::empty({e.E, 2, e.P, e.P}, poses.options());
+  auto order = torch::empty({e.E}, poses.options().dtype(torch::kInt32));
+  const size_t wsb = dpvo_ba_workspace_bytes(e.E, t0, t1);
   auto ws = torch::empty({(int64_t)wsb}, poses.options().dtype(torch::kUInt8));
   check_status(dpvo_reproject_ordered_plan_insert(
-                   poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(),
-                   ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                   poses.numel() / 7, patches.numel() / (3 * P * P), N2, coords.data_ptr<float>(),
-                   order.data_ptr<int32_t>(), t0, t1, ws.data_ptr(), wsb, src.data_ptr(),
-                   ptrs.data(), sc.data(), (int)ptrs.size(), C, H, W, dtype_code(src),
-                   current_stream()),
+                   e.poses, e.patches, e.intrinsics, e.ii, e.jj, e.kk, e.E, e.P, e.num_poses,
+                   e.num_patches, N2, coords.data_ptr<float>(), order.data_ptr<int32_t>(), t0, t1,
+                   ws.data_ptr(), wsb, src.data_ptr(), ptrs.data(), sc.data(), (int)ptrs.size(), C,
+                   H, W, dtype_code(src), current_stream()),
                "cuda_ba.reproject_ordered_plan_insert");
-  return {coords.view({1, E, 2, P, P}), order, ws};
+  return {coords.view({1, e.E, 2, e.P, e.P}), order, ws};
 }
 
 // Device-t0 variants (graph-replayed DPVO updates: the window start moves
@@ -468,59 +462,36 @@ std::vector<torch::Tensor> ba_reproject_ordered_plan_dev(torch::Tensor poses, to
                                                          torch::Tensor intrinsics, torch::Tensor ii,
                                                          torch::Tensor jj, torch::Tensor kk, int N2,
                                                          torch::Tensor t0_dev, int N) {
-  poses = f32_contig(poses, "poses");
-  patches = f32_contig(patches, "patches");
-  intrinsics = f32_contig(intrinsics, "intrinsics");
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int P = patches.size(-1);
-  const int E = ii.numel();
-  TORCH_CHECK(jj.numel() == E && kk.numel() == E, "ii, jj, kk must have equal length");
-  auto coords = torch::empty({E, 2, P, P}, poses.options());
-  auto order = torch::empty({E}, poses.options().dtype(torch::kInt32));
-  const size_t wsb = dpvo_ba_workspace_bytes(E, 0, N);
+  auto coords = torch::empty({e.E, 2, e.P, e.P}, poses.options());
+  auto order = torch::empty({e.E}, poses.options().dtype(torch::kInt32));
+  const size_t wsb = dpvo_ba_workspace_bytes(e.E, 0, N);
   auto ws = torch::empty({(int64_t)wsb}, poses.options().dtype(torch::kUInt8));
   check_status(dpvo_reproject_ordered_plan_dev(
-                   poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(),
-                   ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                   poses.numel() / 7, patches.numel() / (3 * P * P), N2, coords.data_ptr<float>(),
-                   order.data_ptr<int32_t>(), dev_scalar(t0_dev, "t0_dev"), N, ws.data_ptr(), wsb,
-                   current_stream()),
+                   e.poses, e.patches, e.intrinsics, e.ii, e.jj, e.kk, e.E, e.P, e.num_poses,
+                   e.num_patches, N2, coords.data_ptr<float>(), order.data_ptr<int32_t>(),
+                   dev_scalar(t0_dev, "t0_dev"), N, ws.data_ptr(), wsb, current_stream()),
                "cuda_ba.reproject_ordered_plan_dev");
-  return {coords.view({1, E, 2, P, P}), order, ws};
+  return {coords.view({1, e.E, 2, e.P, e.P}), order, ws};
 }
 
 void ba_forward_planned_dev(torch::Tensor ws, torch::Tensor poses, torch::Tensor patches,
                             torch::Tensor intrinsics, torch::Tensor target, torch::Tensor weight,
                             torch::Tensor lmbda, torch::Tensor ii, torch::Tensor jj,
                             torch::Tensor kk, torch::Tensor t0_dev, int N, int iterations) {
-  check_device(poses, "poses");
-  check_device(patches, "patches");
-  TORCH_CHECK(poses.scalar_type() == torch::kFloat32 && patches.scalar_type() == torch::kFloat32,
-              "poses / patches must be float32");
-  TORCH_CHECK(poses.is_contiguous() && patches.is_contiguous(),
-              "poses and patches must be contiguous (updated in place)");
+  const BaIn b = ba_inputs(poses, patches, target, weight, lmbda);
+  const EdgeIn e = edge_inputs(poses, patches, intrinsics, ii, jj, kk);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
-  const int P = patches.size(-1);
-  intrinsics = f32_contig(intrinsics, "intrinsics");
-  target = f32_contig(target, "target");
-  weight = f32_contig(weight, "weight");
-  lmbda = f32_contig(lmbda, "lmbda");
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
-  kk = idx64(kk, "kk");
-  const int E = ii.numel();
-  TORCH_CHECK(jj.numel() == E && kk.numel() == E && target.numel() == 2 * (int64_t)E &&
-                  weight.numel() == 2 * (int64_t)E,
-              "ii / jj / kk / target / weight sizes disagree");
-  check_status(dpvo_ba_forward_planned_dev(
-                   poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(),
-                   target.data_ptr<float>(), weight.data_ptr<float>(), lmbda.data_ptr<float>(),
-                   ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), E, P,
-                   poses.numel() / 7, patches.numel() / (3 * P * P), dev_scalar(t0_dev, "t0_dev"),
-                   N, iterations, ws.data_ptr(), ws.numel(), current_stream()),
+  // exactly 2 E here, where forward / forward_planned accept longer buffers
+  TORCH_CHECK(target.numel() == 2 * (int64_t)e.E && weight.numel() == 2 * (int64_t)e.E,
+              "target / weight must hold 2 E values");
+  // runs under graph capture: no status poll before, no status copy after
+  check_status(dpvo_ba_forward_planned_dev(e.poses, e.patches, e.intrinsics, b.target, b.weight,
+                                           b.lmbda, e.ii, e.jj, e.kk, e.E, e.P, e.num_poses,
+                                           e.num_patches, dev_scalar(t0_dev, "t0_dev"), N,
+                                           iterations, ws.data_ptr(), ws.numel(),
+                                           current_stream()),
                "cuda_ba.forward_planned_dev");
 }
 
@@ -1273,7 +1244,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_marks", [](bool on) { check_status(dpvo_ba_set_marks(on ? 1 : 0), "set_marks"); },
         "stamp wall-clock marks into the BA workspace (instrumentation)");
   m.def("workspace_marks", &ba_workspace_marks,
-        "the 2432 marks of a workspace ([1664 + 2b] / [1665 + 2b]: fused launch workgroup b)");
+        "the DPVO_BA_MARKS marks of a workspace ([1664 + 2b] / [1665 + 2b]: fused launch workgroup b)");
   m.def("forward_dx", &ba_forward_dx, "forward; returns the last iteration's dX [N, 6] (fp64)");
   m.def("last_dx", &ba_last_dx, "dX [N, 6] of the last iteration of a planned forward on ws");
   m.def("reproject_ordered_plan", &ba_reproject_ordered_plan,

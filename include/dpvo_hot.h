@@ -310,7 +310,9 @@ int dpvo_ba_set_status_sink(int* acc);
    dpvo_ba_forward on this workspace stamped -- wall clock (100 MHz): [0]
    start, [1] setup, then linearize, patch, schur, solve, update per iteration;
    shader clock: [38] start, [39] end; [40..] finer stamps inside the setup
-   and the first solve -- copied to the DEVICE array `out`. */
+   and the first solve -- copied to the DEVICE array `out`, DPVO_BA_MARKS
+   int64 long. */
+#define DPVO_BA_MARKS 2432
 int dpvo_ba_phase_marks(const void* workspace, int E, int t0, int t1, int64_t* out, void* stream);
 /* Instrumentation: start / end wall-clock stamps of every workgroup of the
    last Schur launch, [2 x N(N+1)/2] int64 to DEVICE `out`. */

@@ -60,6 +60,147 @@ def test_host_side_argument_validation(lib):
     assert lib.dpvo_lie_forward(2, 0, 0, 4, None, None, None, None) == 3  # RxSO3 not built
 
 
+def test_ba_and_reproject_return_codes(lib):
+    """Return code of every dpvo_ba_* / dpvo_reproject_* export, and which
+    check wins where two apply: OK for E <= 0 first, then INVALID (1), then
+    UNSUPPORTED (3), then WORKSPACE (4).  Every call is rejected on the host:
+    the pointers are dummies, and calls that the window path would accept on a
+    device get a 16-byte workspace.  The literals were recorded from the build
+    before the dispatch was refactored.  (dpvo_ba_set_status_sink is left out:
+    it re-points the process-wide status sink.)"""
+    one, big, small = ctypes.c_void_p(1), ctypes.c_size_t(1 << 30), ctypes.c_size_t(16)
+    # without a device the window path supports nothing; with one it supports
+    # E = 256, N = 7, and then the short workspace is what rejects the call
+    window = lib.dpvo_ba_plan_supported(256, 1, 8, 3)
+    assert window in (0, 1)
+    declined = 4 if window else 3
+    edges, ba = (one,) * 6, (one,) * 9  # poses .. kk without / with target, weight, lmbda
+    out5 = (ctypes.c_int64 * 5)()
+
+    wsb = lib.dpvo_ba_workspace_bytes
+    if window:
+        # the sizes depend on the device: the window scratch lies behind the
+        # multi-kernel layout, and the large-graph layout holds the sort's scratch
+        assert wsb(256, 1, 8) > 139776
+        assert lib.dpvo_ba_plan_offsets(256, 1, 8, out5) == 0 and out5[0] == 139776
+        assert wsb(20000, 0, 8) > 0 and wsb(256, 0, 30) > 0
+    else:
+        assert wsb(256, 1, 8) == 139776
+        assert lib.dpvo_ba_plan_offsets(256, 1, 8, out5) == 3
+        assert wsb(20000, 0, 8) == 135297536  # E > 16384: large-graph layout
+        assert wsb(256, 0, 30) == 109400576   # N > 20: large-graph layout
+    assert [lib.dpvo_ba_select_path(m) for m in (-1, 1, 3, 6, 0)] == [1, 1, 1, 1, 0]
+    assert lib.dpvo_ba_max_free_poses() == 8192
+    assert lib.dpvo_ba_set_marks(0) == 0
+    for P, N in ((1, 7), (20, 7), (3, 17)):  # P < 2, P * P > 64, N > 16
+        assert lib.dpvo_ba_plan_supported(256, 1, 1 + N, P) == 0
+    assert lib.dpvo_ba_plan_supported(20000, 1, 8, 3) == 0
+
+    f = lib.dpvo_ba_build_schur
+    assert f(*ba, 0, 3, 4, 1, 8, one, None, None, None) == 0
+    assert f(*ba, 256, 1, 4, 1, 8, one, None, None, None) == 1     # P
+    assert f(*ba, 256, 3, 4, 8, 1, one, None, None, None) == 1     # t1 < t0
+    assert f(*ba, 256, 3, 4, 1, 8, None, None, None, None) == 1    # workspace
+    assert f(*ba, 256, 3, 4, 0, 21, one, None, None, None) == 3    # N > 20
+    assert f(*ba, 20000, 3, 4, 1, 8, one, None, None, None) == 3   # E > 16384
+    assert f(*ba, 20000, 1, 4, 1, 8, one, None, None, None) == 1   # INVALID before UNSUPPORTED
+    f = lib.dpvo_ba_solve_update
+    assert f(one, one, None, None, 0, 3, 4, 1, 8, one, None, None) == 0
+    assert f(one, one, None, None, 256, 1, 4, 1, 8, one, None, None) == 1
+    assert f(one, one, None, None, 256, 3, 4, 1, 8, None, None, None) == 1
+    assert f(one, one, None, None, 256, 3, 4, 0, 21, one, None, None) == 3
+    for f in (lib.dpvo_ba_last_status, lib.dpvo_ba_phase_marks, lib.dpvo_ba_workgroup_marks):
+        assert f(None, 256, 1, 8, one, None) == 1
+        assert f(one, 256, 1, 8, None, None) == 1
+        assert f(one, 0, 1, 8, one, None) == 1
+    f = lib.dpvo_ba_last_dx
+    assert f(None, 256, 1, 8, one, None) == 1
+    assert f(one, 256, 8, 1, one, None) == 1
+    assert f(one, 0, 1, 8, one, None) == 1
+    assert f(one, 256, 4, 4, one, None) == 0  # N == 0: nothing to copy
+    f = lib.dpvo_ba_status_accumulate
+    assert f(None, 256, 1, 8, one, None) == 1
+    assert f(one, 256, 1, 8, None, None) == 1
+    assert f(one, 0, 1, 8, one, None) == 0
+    assert f(None, 0, 1, 8, one, None) == 1  # INVALID before the E <= 0 no-op here
+
+    f = lib.dpvo_ba_plan_offsets
+    assert f(0, 1, 8, out5) == 1
+    assert f(256, 8, 1, out5) == 1
+    assert f(256, 1, 8, None) == 1
+    assert f(20000, 1, 8, out5) == 3
+    f = lib.dpvo_ba_plan
+    assert f(None, None, None, 0, 0, 0, 8, 1, None, small, None) == 0
+    assert f(one, one, one, 256, 100, 9, 8, 1, one, big, None) == 1
+    assert f(None, one, one, 256, 100, 9, 1, 8, one, big, None) == 1
+    assert f(one, one, one, 256, 0, 9, 1, 8, one, big, None) == 1
+    assert f(one, one, one, 20000, 100, 9, 8, 1, one, small, None) == 1  # INVALID first
+    assert f(one, one, one, 20000, 100, 9, 1, 8, one, small, None) == 3  # UNSUPPORTED before WORKSPACE
+    assert f(one, one, one, 256, 100, 9, 1, 8, one, small, None) == declined
+
+    f = lib.dpvo_ba_forward  # .., E, P, num_poses, num_patches, PPF, t0, t1, iterations, eff_impl
+    assert f(*(None,) * 9, 0, 3, 9, 100, 0, 1, 8, 2, 0, None, small, None) == 0
+    assert f(*ba, 256, 3, 9, 100, 0, 1, 8, 0, 0, one, big, None) == 0      # no iterations
+    assert f(*ba, 256, 1, 9, 100, 0, 1, 8, 2, 0, one, big, None) == 1      # P
+    assert f(*ba, 256, 3, 9, 100, 0, 8, 1, 2, 0, one, big, None) == 1      # t1 < t0
+    assert f(*ba[:8], None, 256, 3, 9, 100, 0, 1, 8, 2, 0, one, big, None) == 1  # kk
+    assert f(*ba, 256, 3, 9, 100, 0, 1, 8, 2, 0, one, small, None) == 4
+    assert f(*ba, 256, 1, 9, 100, 0, 1, 8, 2, 0, one, small, None) == 1    # INVALID before WORKSPACE
+    assert f(*ba, 20000, 3, 9, 100, 0, 1, 8, 2, 0, one, small, None) == 4  # large graph alike
+    f = lib.dpvo_ba_forward_planned  # .., E, P, num_poses, num_patches, t0, t1, iterations
+    assert f(*(None,) * 9, 0, 3, 9, 100, 1, 8, 2, None, small, None) == 0
+    assert f(*ba, 256, 3, 9, 100, 1, 8, 0, one, big, None) == 0
+    assert f(*ba, 256, 1, 9, 100, 1, 8, 2, one, big, None) == 1
+    assert f(*ba, 256, 3, 9, 100, 8, 1, 2, one, big, None) == 1
+    assert f(*ba, 256, 3, 9, 100, 1, 8, 2, None, big, None) == 1
+    assert f(*ba, 20000, 3, 9, 100, 1, 8, 2, one, small, None) == 3
+    assert f(*ba, 256, 20, 9, 100, 1, 8, 2, one, small, None) == 3  # P * P > 64
+    assert f(*ba, 256, 3, 9, 100, 1, 8, 2, one, small, None) == declined
+    f = lib.dpvo_ba_forward_planned_dev  # .., num_patches, t0_dev, N, iterations
+    assert f(*(None,) * 9, 0, 3, 9, 100, None, 7, 2, None, small, None) == 0
+    assert f(*ba, 256, 1, 9, 100, one, 7, 2, one, big, None) == 1
+    assert f(*ba, 256, 3, 9, 100, None, 7, 2, one, big, None) == 1   # t0_dev
+    assert f(*ba, 256, 3, 9, 100, one, -1, 2, one, big, None) == 1   # N < 0
+    assert f(*ba, 256, 3, 9, 100, one, 17, 2, one, small, None) == 3
+    assert f(*ba, 256, 3, 9, 100, one, 7, 2, one, small, None) == declined
+
+    f = lib.dpvo_reproject  # .., E, P, num_poses, num_patches, coords
+    assert f(*edges, 0, 3, 9, 100, one, None) == 0
+    assert f(*edges, 256, 0, 9, 100, one, None) == 1
+    assert f(*edges, 256, 3, 0, 100, one, None) == 1
+    f = lib.dpvo_reproject_ordered  # .., num_patches, N2, coords, order
+    assert f(*edges, 0, 3, 9, 100, 9, one, one, None) == 0
+    assert f(*edges, 256, 3, 9, 0, 9, one, one, None) == 1
+    assert f(*edges, 256, 3, 9, 100, 9, one, None, None) == 1
+    f = lib.dpvo_reproject_ordered_plan  # .., N2, coords, order, t0, t1, workspace, bytes
+    assert f(*(None,) * 6, 0, 3, 9, 100, 9, None, None, 1, 8, None, small, None) == 0
+    assert f(*edges, 256, 3, 9, 100, 9, one, None, 1, 8, one, big, None) == 1
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, 8, 1, one, big, None) == 1
+    assert f(*edges, 20000, 3, 9, 100, 9, one, one, 1, 8, one, small, None) == 3
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, 1, 8, one, small, None) == declined
+    f = lib.dpvo_reproject_ordered_plan_dev  # .., order, t0_dev, N, workspace, bytes
+    assert f(*(None,) * 6, 0, 3, 9, 100, 9, None, None, None, 7, None, small, None) == 0
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, None, 7, one, big, None) == 1
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, one, -1, one, big, None) == 1
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, one, 17, one, small, None) == 3
+    assert f(*edges, 256, 3, 9, 100, 9, one, one, one, 7, one, small, None) == declined
+
+    # .., workspace, bytes, src, dst, scale, L, C, H, W, dtype; dst / scale are read on the host
+    f = lib.dpvo_reproject_ordered_plan_insert
+    dst, scale = (ctypes.c_void_p * 2)(1, 1), (ctypes.c_int * 2)(1, 4)
+    head = (*edges, 256, 3, 9, 100, 9, one, one, 1, 8, one, small)
+    assert f(*(None,) * 6, 0, 3, 9, 100, 9, None, None, 1, 8, None, small, None, None, None, 0, 0,
+             0, 0, 0, None) == 0
+    assert f(*head, None, dst, scale, 2, 64, 32, 32, 0, None) == 1       # src
+    assert f(*head, one, dst, scale, 0, 64, 32, 32, 0, None) == 1        # L
+    assert f(*head, one, dst, scale, 2, 64, 32, 32, 2, None) == 3        # fp64 pyramid
+    assert f(*head, one, dst, scale, 5, 64, 32, 32, 0, None) == 3        # L > 4
+    assert f(*head, one, (ctypes.c_void_p * 2)(1, None), scale, 2, 64, 32, 32, 0, None) == 1
+    assert f(*head, one, dst, (ctypes.c_int * 2)(1, 3), 2, 64, 32, 32, 0, None) == 3
+    assert f(*head[:6], 20000, *head[7:], one, dst, scale, 2, 64, 32, 32, 0, None) == 3
+    assert f(*head, one, dst, scale, 2, 64, 32, 32, 1, None) == declined
+
+
 def test_workspace_size_grows_with_problem(lib):
     a = lib.dpvo_ba_workspace_bytes(256, 1, 8)
     b = lib.dpvo_ba_workspace_bytes(2048, 1, 12)
