@@ -127,9 +127,11 @@ def corr_levels(fmap1, pyramid, coords, ii, jj, radius=3, scales=(1, 4), order=N
     axis and flattened to [B, M, (2R+1)^2 * p^2 * L] float32.  Inference only.
 
     Levels stored channels-last (``synthetic.channels_last`` / ``to_channels_last``)
-    take the matrix-core path (corr_nhwc.hip); NCHW levels the VALU path.
+    take the matrix-core path (corr_nhwc.hip); NCHW levels the matrix-core
+    kernel of corr_nchw.hip where it applies (fp16 / fp32, C = 128, at most 4
+    levels, rows in aligned 8-B pieces), else the VALU kernels (corr.hip).
     float16 features (the fork's MIXED_PRECISION runtime) run on
-    v_mfma_f32_16x16x16_f16 with fp32 accumulation; the output stays float32.
+    v_mfma_f32_16x16x32_f16 with fp32 accumulation; the output stays float32.
     ``order`` (int32 [E], from ``fastba.reproject(..., mem=N2)``): process
     edges grouped by target frame, one group range per XCD (same results)."""
     require_gpu(fmap1)

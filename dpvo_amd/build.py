@@ -43,7 +43,7 @@ EXTENSIONS = {
     "dpvo_encoder": "ext_encoder.cpp",
 }
 HEADERS = ["common.hpp", "ext_common.hpp", "ba_device.hpp", "ba_solve.hpp", "pyr_insert.hpp", "ba_bgj.hpp",
-           "sim3.hpp", "lie_se3.hpp", "ba_paths.hpp"]
+           "sim3.hpp", "lie_se3.hpp", "ba_paths.hpp", "corr_paths.hpp"]
 # per-source device flags.  The BA window kernel is a chain of short dependent
 # steps run by few waves: clang's SLP vectoriser packs its scalar fp32 math into
 # v_pk_fma_f32 and pays for it with register-pair v_mov shuffles (3x the

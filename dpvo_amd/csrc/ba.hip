@@ -1423,21 +1423,17 @@ DPVO_EXPORT int dpvo_reproject_ordered_plan_insert(
     void* stream) {
   if (E <= 0) return DPVO_OK;
   if (P <= 0 || num_poses <= 0 || num_patches <= 0 || !order || !coords || !poses || !patches ||
-      !intrinsics || !ii || !jj || !kk || !workspace || t1 < t0 || !src || !dst || !scale ||
-      L <= 0 || C <= 0 || H <= 0 || W <= 0)
+      !intrinsics || !ii || !jj || !kk || !workspace || t1 < t0 || !src || C <= 0 || H <= 0 ||
+      W <= 0)
     return DPVO_ERR_INVALID;
-  if ((dtype != DPVO_F32 && dtype != DPVO_F16) || L > 4) return DPVO_ERR_UNSUPPORTED;
-  for (int l = 0; l < L; l++) {
-    if (!dst[l]) return DPVO_ERR_INVALID;
-    if (scale[l] != 1 && scale[l] != 2 && scale[l] != 4 && scale[l] != 8)
-      return DPVO_ERR_UNSUPPORTED;
-  }
+  InsLevels lv;
+  if (const int rc = ins_levels(&lv, dst, scale, L, dtype, nullptr, 0, nullptr)) return rc;
   BaWindowWs ws;
   if (const int rc = window_admit(E, t1 - t0, P, workspace, workspace_bytes, &ws)) return rc;
   return ba_window_reproject_plan_insert(
       {const_cast<float*>(poses), const_cast<float*>(patches), intrinsics, nullptr, nullptr,
        nullptr, ii, jj, kk, E, P, num_poses, num_patches, t0, t1 - t0, nullptr},
-      N2, coords, (int*)order, ws, src, dst, scale, L, C, H, W, dtype == DPVO_F16 ? 1 : 0, stream);
+      N2, coords, (int*)order, ws, src, lv, L, C, H, W, dtype == DPVO_F16 ? 1 : 0, stream);
 }
 
 DPVO_EXPORT int dpvo_reproject_ordered_plan_dev(const float* poses, const float* patches,

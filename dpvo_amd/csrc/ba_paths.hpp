@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "corr_paths.hpp"  // InsLevels
 #include "dpvo_hot.h"
 
 namespace dpvo {
@@ -67,12 +68,11 @@ int ba_window_launch(const BaProblem& p, int iterations, const BaWindowWs& ws, v
 // reprojection + A-CORR edge order + plan in one launch, ...
 int ba_window_reproject_plan(const BaProblem& p, int N2, float* coords, int* order,
                              const BaWindowWs& ws, void* stream);
-// ... plus the insertion of the new frame (src [C, H, W] NCHW fp32 / fp16, dst[l]
-// the channels-last slot of level l, scale[l] in {1, 2, 4, 8})
+// ... plus the insertion of the new frame (src [C, H, W] NCHW fp32 / fp16, lv
+// the L levels as corr_paths.hpp's ins_levels filled them)
 int ba_window_reproject_plan_insert(const BaProblem& p, int N2, float* coords, int* order,
-                                    const BaWindowWs& ws, const void* src, void* const* dst,
-                                    const int* scale, int L, int C, int H, int W, int half,
-                                    void* stream);
+                                    const BaWindowWs& ws, const void* src, const InsLevels& lv,
+                                    int L, int C, int H, int W, int half, void* stream);
 
 // ---- ba_large.hip: large graphs (global BA, cfg4)
 size_t gba_workspace_bytes(int E, int N);

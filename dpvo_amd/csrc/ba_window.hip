@@ -2240,26 +2240,15 @@ int ba_window_reproject_plan(const BaProblem& p, int N2, float* coords, int* ord
 }
 
 // reproject + order + plan + frame insertion (src [C, H, W] NCHW fp32 / fp16,
-// dst[l] the channels-last slot of level l, scale[l] in {1, 2, 4, 8})
+// lv: the channels-last slots and scales of the L levels)
 int ba_window_reproject_plan_insert(const BaProblem& p, int N2, float* coords, int* order,
-                                    const BaWindowWs& ws, const void* src, void* const* dst,
-                                    const int* scale, int L, int C, int H, int W, int half,
-                                    void* stream) {
+                                    const BaWindowWs& ws, const void* src, const InsLevels& lv,
+                                    int L, int C, int H, int W, int half, void* stream) {
   set_attrs();
   const Plan plan = plan_view(p, ws);
   const int E = p.E, P = p.P;
   RArgs r = reproject_args(p, N2, coords, order, ws.marks ? ws.marks + kLaunchMarks : nullptr);
-  InsArgs I = {};
-  I.src = src;
-  I.L = L;
-  I.C = C;
-  I.H = H;
-  I.W = W;
-  I.lv.mem = 1;
-  for (int l = 0; l < L; l++) {
-    I.lv.dst[l] = dst[l];
-    I.lv.s[l] = scale[l];
-  }
+  InsArgs I = {src, lv, L, C, H, W};
   I.gx = (W + kInsTX - 1) / kInsTX;
   I.gy = (H + kInsTY - 1) / kInsTY;
   I.ntile = I.gx * I.gy * ((C + kInsTC - 1) / kInsTC);

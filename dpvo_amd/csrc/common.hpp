@@ -62,6 +62,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// wave-uniform per-level parameter without a dynamic index into the kernel
+// argument struct (that would route every access through scratch / flat
+// loads, which count in vmcnt and force full drains in the tile loop)
+template <typename X>
+__device__ __forceinline__ X sel4(int l, X a, X b, X c, X d) {
+  return l == 0 ? a : l == 1 ? b : l == 2 ? c : d;
+}
+
 // Workgroup barrier that orders LDS traffic only (same reasoning one level
 // up): global loads issued before it stay in flight across it.
 __device__ __forceinline__ void lds_barrier() {

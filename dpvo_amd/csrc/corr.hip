@@ -15,16 +15,12 @@
 // SGPR operands of v_fma, and the bilinear + permute is fused into the store
 // phase, which gathers raw values from G in LDS.  No intermediate volume is
 // written to HBM.
+#include <type_traits>
+
 #include "common.hpp"
+#include "corr_paths.hpp"
 
 namespace dpvo {
-
-// corr_nchw.hip: the matrix-core forward for NCHW fp16 / fp32 levels (returns
-// DPVO_ERR_UNSUPPORTED outside its shape; the VALU kernels below take those)
-int corr_nchw_mma(const void* fmap1, const void* const* fmap2, const int* H2, const int* W2,
-                  const float* scale, int L, bool use_scale, const float* coords,
-                  const int64_t* ii, const int64_t* jj, int B, int M, int C, int np, int N1,
-                  int N2, int R, int dtype, void* out_t, float* out_f, hipStream_t s);
 
 constexpr int kCorrWaves = 4;       // waves (edges) per workgroup
 constexpr int kBoxPx = 2 * kWave;   // bounding-box pixels per wave (2 per lane)
@@ -35,7 +31,7 @@ struct CorrLevel {
   float scale;
 };
 struct CorrLevels {
-  CorrLevel lv[8];
+  CorrLevel lv[kCorrValuMaxL];
 };
 
 // Per-wave scratch in LDS: slab (G or raw) + per-patch-pixel geometry.
@@ -270,46 +266,41 @@ static size_t corr_smem_bytes(int R) {
   return sizeof(A) * kCorrWaves * slab + sizeof(CorrGeom<NPT>) * kCorrWaves;
 }
 
-template <typename T>
-static int launch_corr_fwd(const void* fmap1, const void* fmap2, const float* coords,
-                           const int64_t* ii, const int64_t* jj, int B, int M, int C, int np,
-                           int N1, int N2, int H2, int W2, int R, void* out, hipStream_t s) {
-  const dim3 grid((B * M + kCorrWaves - 1) / kCorrWaves), block(kCorrWaves * kWave);
-#define DPVO_CORR_CASE(NPT)                                                                    \
-  if (np <= NPT) {                                                                             \
-    hipLaunchKernelGGL((corr_fwd_kernel<T, NPT>), grid, block,                                 \
-                       (corr_smem_bytes<NPT, typename Acc<T>::type>(R)), s,                    \
-                       (const T*)fmap1, (const T*)fmap2, coords, ii, jj, B, M, C, np, N1, N2,  \
-                       H2, W2, R, (T*)out);                                                    \
-    return launch_status();                                                                    \
-  }
-  DPVO_CORR_CASE(1)
-  DPVO_CORR_CASE(4)
-  DPVO_CORR_CASE(9)
-  DPVO_CORR_CASE(16)
-#undef DPVO_CORR_CASE
+// np = p * p -> the NPT instantiation (1, 4, 9 or 16 patch pixels): f gets NPT
+// as a std::integral_constant.  Forward, forward-levels and backward.
+template <typename F>
+static int with_npt(int np, F f) {
+  if (np <= 1) return f(std::integral_constant<int, 1>());
+  if (np <= 4) return f(std::integral_constant<int, 4>());
+  if (np <= 9) return f(std::integral_constant<int, 9>());
+  if (np <= 16) return f(std::integral_constant<int, 16>());
   return DPVO_ERR_UNSUPPORTED;
 }
 
-template <typename T>
-static int launch_corr_fwd_levels(const void* fmap1, const CorrLevels& lv, int L,
-                                  const float* coords, const int64_t* ii, const int64_t* jj,
-                                  int B, int M, int C, int np, int N1, int N2, int R, float* out,
-                                  hipStream_t s) {
-  const dim3 grid((B * M + kCorrWaves - 1) / kCorrWaves, L), block(kCorrWaves * kWave);
-#define DPVO_CORR_CASE(NPT)                                                                       \
-  if (np <= NPT) {                                                                                \
-    hipLaunchKernelGGL((corr_fwd_levels_kernel<T, NPT>), grid, block,                            \
-                       (corr_smem_bytes<NPT, typename Acc<T>::type>(R)), s,                       \
-                       (const T*)fmap1, lv, L, coords, ii, jj, B, M, C, np, N1, N2, R, out);      \
-    return launch_status();                                                                       \
-  }
-  DPVO_CORR_CASE(1)
-  DPVO_CORR_CASE(4)
-  DPVO_CORR_CASE(9)
-  DPVO_CORR_CASE(16)
-#undef DPVO_CORR_CASE
-  return DPVO_ERR_UNSUPPORTED;
+static CorrLevels corr_levels(const CorrCall& c) {
+  CorrLevels lv = {};
+  for (int l = 0; l < c.L; l++) lv.lv[l] = CorrLevel{c.fmap2[l], c.H2[l], c.W2[l], c.scale[l]};
+  return lv;
+}
+
+// The VALU kernels: one level into out in the fmap dtype (dpvo_corr_forward),
+// or (LEVELS) every level into the stacked float32 output
+template <typename T, bool LEVELS>
+static int launch_corr_valu(const CorrCall& c, hipStream_t s) {
+  const dim3 grid((c.B * c.M + kCorrWaves - 1) / kCorrWaves, LEVELS ? c.L : 1);
+  return with_npt(c.np(), [&](auto npt) {
+    constexpr int NPT = decltype(npt)::value;
+    const size_t lds = corr_smem_bytes<NPT, typename Acc<T>::type>(c.radius);
+    if constexpr (LEVELS)
+      hipLaunchKernelGGL((corr_fwd_levels_kernel<T, NPT>), grid, dim3(kCorrWaves * kWave), lds, s,
+                         (const T*)c.fmap1, corr_levels(c), c.L, c.coords, c.ii, c.jj, c.B, c.M,
+                         c.C, c.np(), c.N1, c.N2, c.radius, (float*)c.out);
+    else
+      hipLaunchKernelGGL((corr_fwd_kernel<T, NPT>), grid, dim3(kCorrWaves * kWave), lds, s,
+                         (const T*)c.fmap1, (const T*)c.fmap2[0], c.coords, c.ii, c.jj, c.B, c.M,
+                         c.C, c.np(), c.N1, c.N2, c.H2[0], c.W2[0], c.radius, (T*)c.out);
+    return launch_status();
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -517,68 +508,75 @@ static inline unsigned grid_for(size_t n, int block = 256) {
 
 using namespace dpvo;
 
+// Every forward entry: select, then launch what was selected.
+static int corr_forward(const CorrCall& c, void* stream) {
+  const CorrChoice ch = corr_select(c);
+  hipStream_t s = as_stream(stream);
+  switch (ch.path) {
+    case DPVO_CORR_PATH_NHWC: return corr_nhwc_launch(c, stream);
+    case DPVO_CORR_PATH_NCHW_MMA:
+    case DPVO_CORR_PATH_NCHW_MMA_ORDERED:
+      if (const int st = corr_nchw_mma(c, ch, stream); st != DPVO_ERR_UNSUPPORTED) return st;
+      [[fallthrough]];  // the LDS attribute could not be set: the VALU kernel
+    case DPVO_CORR_PATH_VALU:
+      if (c.entry == DPVO_CORR_FORWARD) {
+        if (c.dtype == DPVO_F32) return launch_corr_valu<float, false>(c, s);
+        if (c.dtype == DPVO_F16) return launch_corr_valu<__half, false>(c, s);
+        return launch_corr_valu<double, false>(c, s);
+      }
+      if (c.dtype == DPVO_F32) return launch_corr_valu<float, true>(c, s);
+      return launch_corr_valu<__half, true>(c, s);
+  }
+  return ch.status;
+}
+
 DPVO_EXPORT int dpvo_corr_forward(const void* fmap1, const void* fmap2, const float* coords,
                                   const int64_t* ii, const int64_t* jj, int B, int M, int C, int H,
                                   int W, int N1, int N2, int H2, int W2, int radius, int dtype,
                                   void* out, void* stream) {
-  if (B < 0 || M < 0 || C <= 0 || H <= 0 || W <= 0 || radius < 0 || radius > 7 || H2 <= 0 ||
-      W2 <= 0)
-    return DPVO_ERR_INVALID;
-  if (H * W > 16) return DPVO_ERR_UNSUPPORTED;
-  if (B * M == 0) return DPVO_OK;
-  if (!fmap1 || !fmap2 || !coords || !ii || !jj || !out) return DPVO_ERR_INVALID;
-  hipStream_t s = as_stream(stream);
-  const int np = H * W;
-  if (dtype == DPVO_F16 || dtype == DPVO_F32) {
-    const int st = corr_nchw_mma(fmap1, &fmap2, &H2, &W2, nullptr, 1, false, coords, ii, jj, B,
-                                 M, C, np, N1, N2, radius, dtype, out, nullptr, s);
-    if (st != DPVO_ERR_UNSUPPORTED) return st;
-  }
-  switch (dtype) {
-    case DPVO_F32:
-      return launch_corr_fwd<float>(fmap1, fmap2, coords, ii, jj, B, M, C, np, N1, N2, H2, W2,
-                                    radius, out, s);
-    case DPVO_F16:
-      return launch_corr_fwd<__half>(fmap1, fmap2, coords, ii, jj, B, M, C, np, N1, N2, H2, W2,
-                                     radius, out, s);
-    case DPVO_F64:
-      return launch_corr_fwd<double>(fmap1, fmap2, coords, ii, jj, B, M, C, np, N1, N2, H2, W2,
-                                     radius, out, s);
-  }
-  return DPVO_ERR_INVALID;
+  return corr_forward({DPVO_CORR_FORWARD, fmap1, &fmap2, &H2, &W2, nullptr, 1, coords, ii, jj,
+                       nullptr, B, M, C, H, W, N1, N2, radius, dtype, out},
+                      stream);
 }
 
-DPVO_EXPORT int dpvo_corr_forward_levels(const void* fmap1, const void* const* fmap2,
-                                         const int* H2, const int* W2, const float* scale, int L,
-                                         const float* coords, const int64_t* ii,
-                                         const int64_t* jj, int B, int M, int C, int H, int W,
-                                         int N1, int N2, int radius, int dtype, float* out,
-                                         void* stream) {
-  if (L <= 0 || L > 8 || radius < 0 || radius > 7 || C <= 0 || H <= 0 || W <= 0)
-    return DPVO_ERR_INVALID;
-  if (H * W > 16) return DPVO_ERR_UNSUPPORTED;
-  if (B * M == 0) return DPVO_OK;
-  CorrLevels lv = {};
-  for (int l = 0; l < L; l++) {
-    if (!fmap2[l] || H2[l] <= 0 || W2[l] <= 0 || !(scale[l] > 0.f)) return DPVO_ERR_INVALID;
-    lv.lv[l] = CorrLevel{fmap2[l], H2[l], W2[l], scale[l]};
-  }
-  hipStream_t s = as_stream(stream);
-  const int np = H * W;
-  if (dtype == DPVO_F16 || dtype == DPVO_F32) {
-    const int st = corr_nchw_mma(fmap1, fmap2, H2, W2, scale, L, true, coords, ii, jj, B, M, C,
-                                 np, N1, N2, radius, dtype, nullptr, out, s);
-    if (st != DPVO_ERR_UNSUPPORTED) return st;
-  }
-  switch (dtype) {
-    case DPVO_F32:
-      return launch_corr_fwd_levels<float>(fmap1, lv, L, coords, ii, jj, B, M, C, np, N1, N2,
-                                           radius, out, s);
-    case DPVO_F16:
-      return launch_corr_fwd_levels<__half>(fmap1, lv, L, coords, ii, jj, B, M, C, np, N1, N2,
-                                            radius, out, s);
-  }
-  return DPVO_ERR_UNSUPPORTED;
+DPVO_EXPORT int dpvo_corr_forward_levels(
+    const void* fmap1, const void* const* fmap2, const int* H2, const int* W2, const float* scale,
+    int L, const float* coords, const int64_t* ii, const int64_t* jj, int B, int M, int C, int H,
+    int W, int N1, int N2, int radius, int dtype, float* out, void* stream) {
+  return corr_forward({DPVO_CORR_LEVELS, fmap1, fmap2, H2, W2, scale, L, coords, ii, jj, nullptr,
+                       B, M, C, H, W, N1, N2, radius, dtype, out},
+                      stream);
+}
+
+DPVO_EXPORT int dpvo_corr_forward_levels_nhwc_ordered(
+    const void* fmap1, const void* const* fmap2, const int* H2, const int* W2, const float* scale,
+    int L, const float* coords, const int64_t* ii, const int64_t* jj, const int32_t* order, int B,
+    int M, int C, int H, int W, int N1, int N2, int radius, int dtype, float* out, void* stream) {
+  return corr_forward({DPVO_CORR_LEVELS_NHWC, fmap1, fmap2, H2, W2, scale, L, coords, ii, jj,
+                       (const int*)order, B, M, C, H, W, N1, N2, radius, dtype, out},
+                      stream);
+}
+
+DPVO_EXPORT int dpvo_corr_forward_levels_nhwc(
+    const void* fmap1, const void* const* fmap2, const int* H2, const int* W2, const float* scale,
+    int L, const float* coords, const int64_t* ii, const int64_t* jj, int B, int M, int C, int H,
+    int W, int N1, int N2, int radius, int dtype, float* out, void* stream) {
+  return dpvo_corr_forward_levels_nhwc_ordered(fmap1, fmap2, H2, W2, scale, L, coords, ii, jj,
+                                               nullptr, B, M, C, H, W, N1, N2, radius, dtype, out,
+                                               stream);
+}
+
+DPVO_EXPORT int dpvo_corr_query_path(
+    int entry, const void* fmap1, const void* const* fmap2, const int* H2, const int* W2,
+    const float* scale, int L, const float* coords, const int64_t* ii, const int64_t* jj,
+    const int32_t* order, int B, int M, int C, int H, int W, int N1, int N2, int radius, int dtype,
+    const void* out, int* path) {
+  if (!path) return DPVO_ERR_INVALID;
+  const CorrChoice ch = corr_select(
+      {entry, fmap1, fmap2, H2, W2, scale, entry == DPVO_CORR_FORWARD ? 1 : L, coords, ii, jj,
+       (const int*)order, B, M, C, H, W, N1, N2, radius, dtype, const_cast<void*>(out)});
+  *path = ch.path;
+  return ch.status;
 }
 
 DPVO_EXPORT int dpvo_corr_backward(const void* fmap1, const void* fmap2, const float* coords,
@@ -598,19 +596,13 @@ DPVO_EXPORT int dpvo_corr_backward(const void* fmap1, const void* fmap2, const f
   if (B * M == 0) return DPVO_OK;
   const int np = H * W;
   const dim3 grid((B * M + kCorrWaves - 1) / kCorrWaves), block(kCorrWaves * kWave);
-#define DPVO_BWD_CASE(NPT)                                                                     \
-  if (np <= NPT) {                                                                             \
-    hipLaunchKernelGGL((corr_bwd_kernel<float, NPT>), grid, block, corr_smem_bytes<NPT>(radius), \
-                       s, (const float*)fmap1, (const float*)fmap2, coords, ii, jj, grad, B, M, C, \
-                       np, N1, N2, H2, W2, radius, (float*)fmap1_grad, (float*)fmap2_grad);    \
-    return launch_status();                                                                    \
-  }
-  DPVO_BWD_CASE(1)
-  DPVO_BWD_CASE(4)
-  DPVO_BWD_CASE(9)
-  DPVO_BWD_CASE(16)
-#undef DPVO_BWD_CASE
-  return DPVO_ERR_UNSUPPORTED;
+  return with_npt(np, [&](auto npt) {
+    constexpr int NPT = decltype(npt)::value;
+    hipLaunchKernelGGL((corr_bwd_kernel<float, NPT>), grid, block, corr_smem_bytes<NPT>(radius),
+                       s, (const float*)fmap1, (const float*)fmap2, coords, ii, jj, grad, B, M, C,
+                       np, N1, N2, H2, W2, radius, (float*)fmap1_grad, (float*)fmap2_grad);
+    return launch_status();
+  });
 }
 
 DPVO_EXPORT int dpvo_patchify_forward(const void* net, const float* coords, int B, int C, int H,
@@ -620,20 +612,16 @@ DPVO_EXPORT int dpvo_patchify_forward(const void* net, const float* coords, int 
   const int D = 2 * radius + 2;
   const size_t total = (size_t)B * M * C * D * D;
   if (total == 0) return DPVO_OK;
-  hipStream_t s = as_stream(stream);
+  auto launch = [&](auto* o) {
+    using T = std::remove_pointer_t<decltype(o)>;
+    hipLaunchKernelGGL(patchify_fwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0,
+                       as_stream(stream), (const T*)net, coords, B, C, H, W, M, radius, clamp, o);
+    return launch_status();
+  };
   switch (dtype) {
-    case DPVO_F32:
-      hipLaunchKernelGGL(patchify_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s,
-                         (const float*)net, coords, B, C, H, W, M, radius, clamp, (float*)out);
-      return launch_status();
-    case DPVO_F16:
-      hipLaunchKernelGGL(patchify_fwd_kernel<__half>, dim3(grid_for(total)), dim3(256), 0, s,
-                         (const __half*)net, coords, B, C, H, W, M, radius, clamp, (__half*)out);
-      return launch_status();
-    case DPVO_F64:
-      hipLaunchKernelGGL(patchify_fwd_kernel<double>, dim3(grid_for(total)), dim3(256), 0, s,
-                         (const double*)net, coords, B, C, H, W, M, radius, clamp, (double*)out);
-      return launch_status();
+    case DPVO_F32: return launch((float*)out);
+    case DPVO_F16: return launch((__half*)out);
+    case DPVO_F64: return launch((double*)out);
   }
   return DPVO_ERR_INVALID;
 }

@@ -38,17 +38,16 @@
 // v_mfma_f32_16x16x4_f32 forms exact fp32 products (K step s: channels
 // 16u + 4s .. + 3); 8 chunks per level.
 #include "common.hpp"
+#include "corr_paths.hpp"
 
 namespace dpvo {
 namespace {
 
 constexpr int kNcWaves = 4;      // edges per workgroup
-constexpr int kNcC = 128;        // channels (DPVO fmap width)
 constexpr int kNcImgElemBytes = 64;  // channels per LDS image x element bytes
 constexpr int kNcMaxTiles = 17;  // odd; box image <= 272 px
 constexpr int kNcMaxPx = 16 * kNcMaxTiles;
-constexpr int kNcNpMax = 16;     // p * p <= 16 (one MFMA row tile)
-constexpr int kNcMaxL = 4;
+constexpr int kNcNpMax = kCorrNpMax;  // p * p <= 16 (one MFMA row tile)
 // per wave: the image (32 fp16 / 16 fp32 channels x P; reused as G: np x P
 // floats <= 16 x 272, or the slow path's np x D x D <= 16 x 256) + geometry
 constexpr int kNcImgBytes = kNcImgElemBytes * kNcMaxPx;
@@ -91,11 +90,6 @@ __device__ __forceinline__ h4 tr_read(const char* lds) {
   const s4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s4*)(lds));
   return __builtin_bit_cast(h4, v);
-}
-
-template <typename X>
-__device__ __forceinline__ X nc_sel(int l, X a, X b, X c, X d) {
-  return l == 0 ? a : l == 1 ? b : l == 2 ? c : d;
 }
 
 // The matrix-core part of one edge at one level: G[k][px] for every image
@@ -362,7 +356,6 @@ __device__ __forceinline__ void nc_edge(const T* __restrict__ fmap1, const T* __
 // counts gives the rank of every match, and the owner of each wanted rank
 // writes its edge id.  Edge ids are a bijection of positions, so the results
 // are those of the unordered launch (every edge writes only its own output).
-constexpr int kOrdMaxE = 16384, kOrdMaxN2 = 2048;
 
 __device__ __forceinline__ int ord_bin(int64_t v, int N2) {
   return (v >= 0 && v < N2) ? (int)v : N2;  // out-of-range indices: one last bin
@@ -473,19 +466,17 @@ __global__ void __launch_bounds__(kNcWaves* kWave, 2)  // 2 workgroups (8 waves)
   const int l = blockIdx.y;
   const int b = unit / M, m = unit % M;
   const int ix = wave_uniform((int)ii[m]), jx = wave_uniform((int)jj[m]);
-  const T* f2 = reinterpret_cast<const T*>(nc_sel(l, lv.f2[0], lv.f2[1], lv.f2[2], lv.f2[3]));
-  const int H2 = nc_sel(l, lv.H2[0], lv.H2[1], lv.H2[2], lv.H2[3]);
-  const int W2 = nc_sel(l, lv.W2[0], lv.W2[1], lv.W2[2], lv.W2[3]);
-  const int pb = nc_sel(l, lv.pb[0], lv.pb[1], lv.pb[2], lv.pb[3]);
-  const float s = nc_sel(l, lv.scale[0], lv.scale[1], lv.scale[2], lv.scale[3]);
+  const T* f2 = reinterpret_cast<const T*>(sel4(l, lv.f2[0], lv.f2[1], lv.f2[2], lv.f2[3]));
+  const int H2 = sel4(l, lv.H2[0], lv.H2[1], lv.H2[2], lv.H2[3]);
+  const int W2 = sel4(l, lv.W2[0], lv.W2[1], lv.W2[2], lv.W2[3]);
+  const int pb = sel4(l, lv.pb[0], lv.pb[1], lv.pb[2], lv.pb[3]);
+  const float s = sel4(l, lv.scale[0], lv.scale[1], lv.scale[2], lv.scale[3]);
   nc_edge<T>(fmap1, f2, H2, W2, pb, s, use_scale != 0, coords, b, m, ix, jx, M, np, N1, N2, R,
              wlds, out_t, out_f, L, l);
 }
 
 template <typename T>
-int nc_launch(const void* fmap1, const NcLevels& lv, bool use_scale, const float* coords,
-              const int64_t* ii, const int64_t* jj, int B, int M, int np, int N1, int N2, int R,
-              int L, int ordered, void* out_t, float* out_f, hipStream_t s) {
+int nc_launch(const CorrCall& c, const NcLevels& lv, int ordered, hipStream_t s) {
   // 4 x 17.7 KB per workgroup (+ the order's 4 edge ids): above 64 KB, set
   // once per device; if the attribute cannot be set the caller's VALU kernel
   // runs instead (DPVO_ERR_UNSUPPORTED)
@@ -501,63 +492,30 @@ int nc_launch(const void* fmap1, const NcLevels& lv, bool use_scale, const float
     }
     attr[dev] = true;
   }
-  unsigned gx = (unsigned)(((long long)B * M + kNcWaves - 1) / kNcWaves);
+  unsigned gx = (unsigned)(((long long)c.B * c.M + kNcWaves - 1) / kNcWaves);
   if (ordered) gx = 8u * ((gx + 7u) / 8u);
-  const dim3 grid(gx, L), block(kNcWaves * kWave);
+  const dim3 grid(gx, c.L), block(kNcWaves * kWave);
+  const bool single = c.entry == DPVO_CORR_FORWARD;  // out in the fmap dtype, no scale
   hipLaunchKernelGGL(corr_nchw_kernel<T>, grid, block, (size_t)kNcWaves * kNcWaveBytes + 16, s,
-                     (const T*)fmap1, lv, use_scale ? 1 : 0, coords, ii, jj, B, M, np, N1, N2, R,
-                     L, ordered, (T*)out_t, out_f);
+                     (const T*)c.fmap1, lv, single ? 0 : 1, c.coords, c.ii, c.jj, c.B, c.M, c.np(),
+                     c.N1, c.N2, c.radius, c.L, ordered, single ? (T*)c.out : (T*)nullptr,
+                     single ? (float*)nullptr : (float*)c.out);
   return launch_status();
 }
 
 }  // namespace
 
-// The matrix-core NCHW forward, or DPVO_ERR_UNSUPPORTED when the call is
-// outside its shape (then the caller runs corr.hip's VALU kernel): fp16 or
-// fp32, C = 128, p*p <= 16, L <= 4, every level with 8-B pieces at least
-// (W2 and the base aligned to 8 B).  out_t: [B, M, Dp, Dp, p, p] in the fmap
-// dtype (L = 1); else out_f [.., L] float32.
-int corr_nchw_mma(const void* fmap1, const void* const* fmap2, const int* H2, const int* W2,
-                  const float* scale, int L, bool use_scale, const float* coords,
-                  const int64_t* ii, const int64_t* jj, int B, int M, int C, int np, int N1,
-                  int N2, int R, int dtype, void* out_t, float* out_f, hipStream_t s) {
-  if ((dtype != DPVO_F16 && dtype != DPVO_F32) || C != kNcC || np < 1 || np > kNcNpMax ||
-      L < 1 || L > kNcMaxL || R < 0 || R > 7)
-    return DPVO_ERR_UNSUPPORTED;
-  if (out_t && L != 1) return DPVO_ERR_INVALID;
-  if (reinterpret_cast<uintptr_t>(fmap1) % 16) return DPVO_ERR_UNSUPPORTED;
-  const int es = dtype == DPVO_F16 ? 2 : 4;
+// The matrix-core NCHW forward of a call corr_select sent here (fp16 or fp32,
+// C = 128, p*p <= 16, L <= 4, every level in the 8-B or 16-B pieces of ch.pb)
+int corr_nchw_mma(const CorrCall& c, const CorrChoice& ch, void* stream) {
   NcLevels lv = {};
-  for (int l = 0; l < L; l++) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(fmap2[l]);
-    int pb = 0;  // widest piece whose alignment every row start keeps
-    if ((W2[l] * es) % 16 == 0 && p % 16 == 0) pb = 16;
-    else if ((W2[l] * es) % 8 == 0 && p % 8 == 0) pb = 8;
-    if (!pb || H2[l] <= 0) return DPVO_ERR_UNSUPPORTED;
-    lv.f2[l] = fmap2[l];
-    lv.H2[l] = H2[l];
-    lv.W2[l] = W2[l];
-    lv.pb[l] = pb;
-    lv.scale[l] = scale ? scale[l] : 1.0f;
+  for (int l = 0; l < c.L; l++) {
+    lv.f2[l] = c.fmap2[l], lv.H2[l] = c.H2[l], lv.W2[l] = c.W2[l], lv.pb[l] = ch.pb[l];
+    lv.scale[l] = c.scale ? c.scale[l] : 1.0f;
   }
-  if ((long long)B * M == 0) return DPVO_OK;
-  // XCD-aware order for a single batch of a DPVO-sized graph, when some level's
-  // ring is larger than the L2s together (8 x 4 MB): the order's prologue costs
-  // ~6 us per workgroup and pays only where lines are re-fetched from the
-  // Infinity Cache / HBM (cfg2 fp16 level 1, 177 MB: 51 -> 31 us; level 4,
-  // 11 MB: 21 -> 23 us)
-  size_t ring = 0;
-  for (int l = 0; l < L; l++) {
-    const size_t r = (size_t)N2 * kNcC * H2[l] * W2[l] * es;
-    ring = r > ring ? r : ring;
-  }
-  const int ordered = B == 1 && M <= kOrdMaxE && N2 >= 1 && N2 <= kOrdMaxN2 &&
-                      ring > ((size_t)32 << 20);
-  if (dtype == DPVO_F16)
-    return nc_launch<__half>(fmap1, lv, use_scale, coords, ii, jj, B, M, np, N1, N2, R, L,
-                             ordered, out_t, out_f, s);
-  return nc_launch<float>(fmap1, lv, use_scale, coords, ii, jj, B, M, np, N1, N2, R, L, ordered,
-                          out_t, out_f, s);
+  const int ordered = ch.path == DPVO_CORR_PATH_NCHW_MMA_ORDERED;
+  if (c.dtype == DPVO_F16) return nc_launch<__half>(c, lv, ordered, as_stream(stream));
+  return nc_launch<float>(c, lv, ordered, as_stream(stream));
 }
 
 }  // namespace dpvo

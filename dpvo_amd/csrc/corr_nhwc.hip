@@ -19,15 +19,14 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "corr_paths.hpp"
 #include "pyr_insert.hpp"
 
 
 namespace dpvo {
 
-constexpr int kNhwcC = 128;     // channels (DPVO gmap / fmap width)
-constexpr int kMaxL = 4;        // levels per launch
-constexpr int kOutPerLane = 8;  // (2R+1)^2 * p*p <= 512 outputs per level
-constexpr int kNpMax = 16;      // p*p <= 16 (one MFMA row tile)
+constexpr int kOutPerLane = kNhwcMaxOut / kWave;  // (2R+1)^2 * p*p <= 512 outputs per level
+constexpr int kNpMax = kCorrNpMax;                // p*p <= 16 (one MFMA row tile)
 
 struct NhwcLevels {
   const void* f2[kMaxL];  // float or __half, [B, N2, H, W, C]
@@ -45,13 +44,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // makes the wait before each tile drain the whole ring
 typedef const __attribute__((address_space(1))) u32x4 gu32x4;
 
-// wave-uniform per-level parameter without a dynamic index into the kernel
-// argument struct (that would route every access through scratch / flat
-// loads, which count in vmcnt and force full drains in the tile loop)
-template <typename X>
-__device__ __forceinline__ X sel4(int l, X a, X b, X c, X d) {
-  return l == 0 ? a : l == 1 ? b : l == 2 ? c : d;
-}
 #define LV_SEL(field, l) sel4((l), lv.field[0], lv.field[1], lv.field[2], lv.field[3])
 
 // ---------------------------------------------------------------------------
@@ -76,8 +68,6 @@ __device__ __forceinline__ X sel4(int l, X a, X b, X c, X d) {
 // patch, 32 registers) and writes its level's slice of the edge's [nout][L]
 // output block.
 // ---------------------------------------------------------------------------
-constexpr int kLvlMaxTiles = 10;                   // box up to 160 pixels on the matrix path
-constexpr int kLvlBoxStride = 16 * kLvlMaxTiles + 4;
 constexpr int kLvlStage = 16 * 128;                // bytes: 16 pixels x one 128-B line
 
 struct LvlGeom {
@@ -549,51 +539,31 @@ __global__ void __launch_bounds__(256)
   ins_tile<T>(src, lv, L, C, H, W, blockIdx.x, blockIdx.y, blockIdx.z, threadIdx.x, true, tile);
 }
 
-}  // namespace dpvo
-
-using namespace dpvo;
-
-DPVO_EXPORT int dpvo_corr_forward_levels_nhwc_ordered(
-    const void* fmap1, const void* const* fmap2, const int* H2, const int* W2, const float* scale,
-    int L, const float* coords, const int64_t* ii, const int64_t* jj, const int32_t* order, int B,
-    int M, int C, int H, int W, int N1, int N2, int radius, int dtype, float* out, void* stream) {
-  if (L <= 0 || radius < 0 || radius > 7 || C <= 0 || H <= 0 || W <= 0) return DPVO_ERR_INVALID;
-  const int np = H * W, Dp = 2 * radius + 1;
-  if ((dtype != DPVO_F32 && dtype != DPVO_F16) || C != kNhwcC || L > kMaxL || np > kNpMax ||
-      Dp * Dp * np > kOutPerLane * kWave)
-    return DPVO_ERR_UNSUPPORTED;
-  if (B * M == 0) return DPVO_OK;
-  if (!fmap1 || !coords || !ii || !jj || !out) return DPVO_ERR_INVALID;
+// The launch of a call corr_select sent here
+int corr_nhwc_launch(const CorrCall& c, void* stream) {
+  const int L = c.L, np = c.np(), radius = c.radius;
   NhwcLevels lv = {};
-  for (int l = 0; l < L; l++) {
-    if (!fmap2[l] || H2[l] <= 0 || W2[l] <= 0 || !(scale[l] > 0.f)) return DPVO_ERR_INVALID;
-    lv.f2[l] = fmap2[l];
-    lv.H2[l] = H2[l];
-    lv.W2[l] = W2[l];
-    lv.scale[l] = scale[l];
-  }
-  // G: np rows x kLvlBoxStride per wave; the raw path (boxes past
-  // kLvlMaxTiles tiles) keeps np x D x D raw dot products there
-  const int D = 2 * radius + 2;
-  if (D * D > kLvlBoxStride) return DPVO_ERR_UNSUPPORTED;
-  const bool ordered = order && B == 1;
-  const int* ord = ordered ? (const int*)order : (const int*)nullptr;
+  for (int l = 0; l < L; l++)
+    lv.f2[l] = c.fmap2[l], lv.H2[l] = c.H2[l], lv.W2[l] = c.W2[l], lv.scale[l] = c.scale[l];
+  const bool ordered = c.order && c.B == 1;
+  const int* ord = ordered ? c.order : (const int*)nullptr;
   hipStream_t st = as_stream(stream);
   // one wave per (edge, level) unit, two units per wave, whole-line tiles
   const int npair = corr_lvl_npos(L);
   const size_t lsm = (size_t)npair * L * corr_lvl_wave_bytes(np, radius);
-  const unsigned per = ordered ? (unsigned)((M + 7) / 8) : (unsigned)(B * M);
+  const unsigned per = ordered ? (unsigned)((c.M + 7) / 8) : (unsigned)(c.B * c.M);
   const unsigned nwg = ((corr_lvl_paired(L) ? (per + 1) / 2 : per) + npair - 1) / npair;
   const unsigned lg = ordered ? 8u * nwg : nwg;
   const dim3 g(lg), blk(npair * L * kWave);
   const bool r9 = np == 9 && radius == 3;  // DPVO: p = 3, R = 3
 #define LVL_LAUNCH(TT, R9, PR)                                                                \
-  hipLaunchKernelGGL((corr_nhwc_lvl_kernel<TT, 2, R9, PR>), g, blk, lsm, st, (const TT*)fmap1, lv, \
-                     L, coords, ii, jj, B, M, np, N1, N2, radius, ord, out)
+  hipLaunchKernelGGL((corr_nhwc_lvl_kernel<TT, 2, R9, PR>), g, blk, lsm, st, (const TT*)c.fmap1, \
+                     lv, L, c.coords, c.ii, c.jj, c.B, c.M, np, c.N1, c.N2, radius, ord,      \
+                     (float*)c.out)
 #define LVL_LAUNCH_P(TT, R9)              \
   if (corr_lvl_paired(L)) LVL_LAUNCH(TT, R9, true); \
   else LVL_LAUNCH(TT, R9, false)
-  if (dtype == DPVO_F32) {
+  if (c.dtype == DPVO_F32) {
     if (r9) { LVL_LAUNCH_P(float, true); } else { LVL_LAUNCH_P(float, false); }
   } else {
     if (r9) { LVL_LAUNCH_P(__half, true); } else { LVL_LAUNCH_P(__half, false); }
@@ -603,16 +573,9 @@ DPVO_EXPORT int dpvo_corr_forward_levels_nhwc_ordered(
   return launch_status();
 }
 
-DPVO_EXPORT int dpvo_corr_forward_levels_nhwc(const void* fmap1, const void* const* fmap2,
-                                              const int* H2, const int* W2, const float* scale,
-                                              int L, const float* coords, const int64_t* ii,
-                                              const int64_t* jj, int B, int M, int C, int H,
-                                              int W, int N1, int N2, int radius, int dtype,
-                                              float* out, void* stream) {
-  return dpvo_corr_forward_levels_nhwc_ordered(fmap1, fmap2, H2, W2, scale, L, coords, ii, jj,
-                                               nullptr, B, M, C, H, W, N1, N2, radius, dtype, out,
-                                               stream);
-}
+}  // namespace dpvo
+
+using namespace dpvo;
 
 DPVO_EXPORT int dpvo_feature_to_nhwc(const void* src, void* dst, int count, int C, int H, int W,
                                      int dtype, void* stream) {
@@ -621,36 +584,23 @@ DPVO_EXPORT int dpvo_feature_to_nhwc(const void* src, void* dst, int count, int 
   const int HW = H * W;
   const dim3 grid((HW + 31) / 32, (C + 31) / 32, count), block(256);
   hipStream_t s = as_stream(stream);
-  switch (dtype) {
-    case DPVO_F32:
-      hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, block, 0, s, (const float*)src,
-                         (float*)dst, C, HW);
-      return launch_status();
-    case DPVO_F16:
-      hipLaunchKernelGGL(nchw_to_nhwc_kernel<__half>, grid, block, 0, s, (const __half*)src,
-                         (__half*)dst, C, HW);
-      return launch_status();
-  }
-  return DPVO_ERR_UNSUPPORTED;
+  if (dtype == DPVO_F32)
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, block, 0, s, (const float*)src,
+                       (float*)dst, C, HW);
+  else if (dtype == DPVO_F16)
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<__half>, grid, block, 0, s, (const __half*)src,
+                       (__half*)dst, C, HW);
+  else
+    return DPVO_ERR_UNSUPPORTED;
+  return launch_status();
 }
 
 static int pyramid_insert_impl(const void* src, void* const* dst, const int* scale, int L, int C,
                                int H, int W, int dtype, void* stream, const int32_t* slot_dev,
                                int mem, const int64_t* slot_bytes) {
-  if (!src || !dst || !scale || L <= 0 || C <= 0 || H <= 0 || W <= 0) return DPVO_ERR_INVALID;
-  if ((dtype != DPVO_F32 && dtype != DPVO_F16) || L > kMaxL) return DPVO_ERR_UNSUPPORTED;
-  if (slot_dev && (mem <= 0 || !slot_bytes)) return DPVO_ERR_INVALID;
-  InsLevels lv = {};
-  lv.slot_dev = (const int*)slot_dev;
-  lv.mem = mem > 0 ? mem : 1;
-  for (int l = 0; l < L && slot_dev; l++) lv.slot_bytes[l] = slot_bytes[l];
-  for (int l = 0; l < L; l++) {
-    const int s = scale[l];
-    if (!dst[l]) return DPVO_ERR_INVALID;
-    if (s != 1 && s != 2 && s != 4 && s != 8) return DPVO_ERR_UNSUPPORTED;
-    lv.dst[l] = dst[l];
-    lv.s[l] = s;
-  }
+  if (!src || C <= 0 || H <= 0 || W <= 0) return DPVO_ERR_INVALID;
+  InsLevels lv;
+  if (const int rc = ins_levels(&lv, dst, scale, L, dtype, slot_dev, mem, slot_bytes)) return rc;
   const dim3 grid((W + kInsTX - 1) / kInsTX, (H + kInsTY - 1) / kInsTY, (C + kInsTC - 1) / kInsTC);
   if (dtype == DPVO_F16)
     hipLaunchKernelGGL(pyramid_insert_kernel<__half>, grid, dim3(256), 0, as_stream(stream),

@@ -7,25 +7,15 @@
 #pragma once
 
 #include "common.hpp"
+#include "corr_paths.hpp"  // InsLevels
 
 namespace dpvo {
 
-constexpr int kInsMaxL = 4;  // levels per insertion
 // 8 x 16 pixel x 32 channel tiles: 600 workgroups for a 160 x 120 x 128 frame, all
 // resident at once (32 x 8 x 32 tiles gave 300: 1.2 rounds over 256 CUs, the tail
 // round nearly empty)
 constexpr int kInsTY = 8, kInsTX = 16, kInsTC = 32;
 constexpr int kInsCS = kInsTY * kInsTX + 1;  // channel stride (+1: no bank conflicts)
-
-struct InsLevels {
-  void* dst[kInsMaxL];  // float or __half (the source's dtype)
-  int s[kInsMaxL];
-  // ring variant (graph-replayed frames): dst[l] is slot 0 of level l, the
-  // slot is *slot_dev % mem, slots slot_bytes[l] apart; null = dst as given
-  const int* slot_dev;
-  int mem;
-  long long slot_bytes[kInsMaxL];
-};
 
 // level-1 copy of the LDS tile: one float4 (4 channels) per lane, 8 lanes per
 // pixel = one 128-B run of the channels-last row

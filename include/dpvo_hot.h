@@ -71,9 +71,9 @@ int dpvo_corr_forward_levels(const void* fmap1, const void* const* fmap2, const 
 /* A-CORR, all levels, channels-last pyramid (no reference counterpart: the
    layout is this build's; semantics identical to dpvo_corr_forward_levels).
    fmap2[l] is [B,N2,H2[l],W2[l],C] (a [B,N2,C,H,W] tensor in channels-last
-   memory), fp32, C == 128, L <= 4, H*W <= 16, (2R+1)^2*H*W <= 512.
-   Returns DPVO_ERR_UNSUPPORTED outside that envelope (callers fall back to
-   dpvo_corr_forward_levels on NCHW data). */
+   memory), fp32 or fp16, C == 128, L <= 4, H*W <= 16, (2R+1)^2*H*W <= 512,
+   (2R+2)^2 <= 164.  Returns DPVO_ERR_UNSUPPORTED outside that envelope
+   (callers fall back to dpvo_corr_forward_levels on NCHW data). */
 int dpvo_corr_forward_levels_nhwc(const void* fmap1, const void* const* fmap2, const int* H2,
                                   const int* W2, const float* scale, int L, const float* coords,
                                   const int64_t* ii, const int64_t* jj, int B, int M, int C,
@@ -90,6 +90,25 @@ int dpvo_corr_forward_levels_nhwc_ordered(const void* fmap1, const void* const* 
                                           const int64_t* jj, const int32_t* order, int B, int M,
                                           int C, int H, int W, int N1, int N2, int radius,
                                           int dtype, float* out, void* stream);
+/* Which kernel a forward entry would run, without a device: the status the
+   entry returns before it launches, and through *path the kernel (NONE:
+   rejected, or nothing to do).  entry says which export is meant; the other
+   arguments are that export's (dpvo_corr_forward: fmap2 / H2 / W2 arrays of
+   one level, scale ignored; order: the ordered channels-last entry only).
+   Device pointers are looked at for their alignment only. */
+enum { DPVO_CORR_FORWARD = 0, DPVO_CORR_LEVELS = 1, DPVO_CORR_LEVELS_NHWC = 2 };
+enum {
+  DPVO_CORR_PATH_NONE = 0,
+  DPVO_CORR_PATH_NHWC = 1,             /* channels-last levels, matrix cores */
+  DPVO_CORR_PATH_NCHW_MMA = 2,         /* NCHW levels, matrix cores */
+  DPVO_CORR_PATH_NCHW_MMA_ORDERED = 3, /* the same, edges grouped by target frame */
+  DPVO_CORR_PATH_VALU = 4
+};
+int dpvo_corr_query_path(int entry, const void* fmap1, const void* const* fmap2, const int* H2,
+                         const int* W2, const float* scale, int L, const float* coords,
+                         const int64_t* ii, const int64_t* jj, const int32_t* order, int B, int M,
+                         int C, int H, int W, int N1, int N2, int radius, int dtype,
+                         const void* out, int* path);
 /* Feature maps [count,C,H,W] -> channels-last [count,H,W,C] (the per-frame
    cost of keeping a channels-last pyramid; dtype F32 or F16). */
 int dpvo_feature_to_nhwc(const void* src, void* dst, int count, int C, int H, int W, int dtype,

@@ -9,7 +9,8 @@ means to run one branch therefore has to prove that its inputs reach it:
 `nhwc_supported`, `nchw_mma_supported`, `nchw_ordered`, `unit_classes`,
 `valu_fast` and `nchw_modes` restate the predicates and the kernels' box
 arithmetic, the tables below say which branch every case is for, and the CPU
-test checks the two against each other.  No GPU, no test functions."""
+test checks the two against each other and the predicates against the native
+selection (dpvo_corr_query_path).  No GPU, no test functions."""
 import numpy as np
 import torch
 
@@ -155,8 +156,8 @@ def nhwc_supported(p_h, p_w, R, C, L, dtype):
 
 
 def nchw_mma_supported(p_h, p_w, R, C, L, level_shapes, dtype):
-    """corr_nchw_mma's host predicate for 16-B aligned level bases: else the
-    VALU kernels of corr.hip run."""
+    """corr_select's predicate (corr_paths.hpp) for the NCHW matrix-core kernel,
+    for 16-B aligned level bases: else the VALU kernels of corr.hip run."""
     if dtype not in (torch.float32, torch.float16) or C != 128:
         return False
     if not (1 <= p_h * p_w <= 16 and 1 <= L <= kNcMaxL and 0 <= R <= 7):
@@ -166,7 +167,7 @@ def nchw_mma_supported(p_h, p_w, R, C, L, level_shapes, dtype):
 
 
 def nchw_ordered(B, M, N2, level_shapes, dtype):
-    """Whether corr_nchw_mma runs its ordered prologue (nc_order)."""
+    """Whether corr_select picks the ordered launch (nc_order's prologue)."""
     es = 2 if dtype == torch.float16 else 4
     ring = max(N2 * 128 * H2 * W2 * es for H2, W2 in level_shapes)
     return B == 1 and M <= kOrdMaxE and 1 <= N2 <= kOrdMaxN2 and ring > (32 << 20)

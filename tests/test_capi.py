@@ -201,6 +201,268 @@ def test_ba_and_reproject_return_codes(lib):
     assert f(*head, one, dst, scale, 2, 64, 32, 32, 1, None) == declined
 
 
+def _levels(L, fmap2=1, H2=8, W2=8, scale=1.0, at=0):
+    """Host level arrays (fmap2, H2, W2, scale) of L good levels; a keyword
+    replaces the value of level `at`."""
+    f = (ctypes.c_void_p * max(L, 1))(*[1] * L)
+    h = (ctypes.c_int * max(L, 1))(*[8] * L)
+    w = (ctypes.c_int * max(L, 1))(*[8] * L)
+    s = (ctypes.c_float * max(L, 1))(*[1.0] * L)
+    if L > 0:
+        f[at], h[at], w[at], s[at] = fmap2, H2, W2, scale
+    return f, h, w, s
+
+
+def test_corr_return_codes(lib):
+    """Return code of every dpvo_corr_* / dpvo_patchify_* / dpvo_feature_*
+    export, and which check wins where two apply.  Every row is answered on
+    the host before any launch or memset (the device pointers are dummies; the
+    level arrays are real host arrays, the entries read them).  The literals
+    of the first block were recorded from the build before the A-CORR host
+    layer was refactored; the second block holds the checks that refactor
+    added."""
+    one, nan = ctypes.c_void_p(1), float("nan")
+    OK, INVALID, UNSUPPORTED = 0, 1, 3
+    p5 = (one,) * 5
+
+    # ---- dpvo_corr_forward: fmap1, fmap2, coords, ii, jj, B, M, C, H, W, N1, N2, H2, W2,
+    #      radius, dtype, out
+    f = lib.dpvo_corr_forward
+    for B, M, C, H, W, H2, W2, R in ((-1, 4, 128, 3, 3, 8, 8, 3), (1, -4, 128, 3, 3, 8, 8, 3),
+                                     (1, 4, 0, 3, 3, 8, 8, 3), (1, 4, 128, 0, 3, 8, 8, 3),
+                                     (1, 4, 128, 3, 0, 8, 8, 3), (1, 4, 128, 3, 3, 0, 8, 3),
+                                     (1, 4, 128, 3, 3, 8, 0, 3), (1, 4, 128, 3, 3, 8, 8, -1),
+                                     (1, 4, 128, 3, 3, 8, 8, 8)):
+        assert f(*p5, B, M, C, H, W, 9, 4, H2, W2, R, 0, one, None) == INVALID
+    for k in range(5):  # each null input with work to do
+        p = p5[:k] + (None,) + p5[k + 1:]
+        assert f(*p, 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 0, one, None) == INVALID
+    assert f(*p5, 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 0, None, None) == INVALID      # out
+    assert f(*p5, 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 7, one, None) == INVALID       # unknown dtype
+    assert f(*p5, 1, 4, 128, 5, 4, 9, 4, 8, 8, 3, 0, one, None) == UNSUPPORTED   # H * W > 16
+    assert f(*p5, 0, 4, 128, 3, 3, 9, 4, 8, 8, 3, 0, one, None) == OK
+    assert f(*p5, 1, 0, 128, 3, 3, 9, 4, 8, 8, 3, 1, one, None) == OK
+    # two checks
+    assert f(*p5, 1, 4, 128, 5, 5, 9, 4, 8, 8, 8, 0, one, None) == INVALID       # radius, H * W
+    assert f(*p5, 1, 0, 128, 5, 5, 9, 4, 8, 8, 3, 0, one, None) == UNSUPPORTED   # H * W, no work
+    assert f(*p5, 1, 0, 128, 3, 3, 9, 4, 0, 8, 3, 0, one, None) == INVALID       # H2, no work
+    assert f(*(None,) * 5, 1, 4, 128, 5, 5, 9, 4, 8, 8, 3, 0, None, None) == UNSUPPORTED
+    assert f(*(None,) * 5, 1, 0, 128, 3, 3, 9, 4, 8, 8, 3, 0, None, None) == OK  # null, no work
+    assert f(*p5, 1, 4, 128, 5, 5, 9, 4, 8, 8, 3, 7, one, None) == UNSUPPORTED   # dtype, H * W
+    assert f(*p5, 1, 0, 128, 3, 3, 9, 4, 8, 8, 3, 7, one, None) == OK            # dtype, no work
+    assert f(None, *p5[1:], 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 7, one, None) == INVALID
+
+    # ---- dpvo_corr_forward_levels: fmap1, fmap2[], H2[], W2[], scale[], L, coords, ii, jj,
+    #      B, M, C, H, W, N1, N2, radius, dtype, out
+    f = lib.dpvo_corr_forward_levels
+    good = _levels(2)
+
+    def lv(arrs, L, B=1, M=4, C=128, H=3, W=3, R=3, dtype=0):
+        return lib.dpvo_corr_forward_levels(one, *arrs, L, one, one, one, B, M, C, H, W, 9, 4, R,
+                                            dtype, one, None)
+
+    assert lv(good, 0) == INVALID and lv(_levels(8), 9) == INVALID
+    assert lv(good, 2, R=-1) == INVALID and lv(good, 2, R=8) == INVALID
+    assert lv(good, 2, C=0) == INVALID and lv(good, 2, H=0) == INVALID
+    assert lv(good, 2, W=0) == INVALID
+    for bad in (dict(fmap2=None), dict(H2=0), dict(W2=-3), dict(scale=0.0), dict(scale=nan)):
+        assert lv(_levels(2, at=1, **bad), 2) == INVALID
+    assert lv(good, 2, H=5, W=4) == UNSUPPORTED
+    assert lv(good, 2, dtype=2) == UNSUPPORTED        # fp64: the single-level entry only
+    assert lv(good, 2, dtype=7) == UNSUPPORTED
+    assert lv(good, 2, M=0) == OK and lv(good, 2, B=0) == OK
+    assert lv(_levels(8), 8, M=0) == OK               # the VALU entry takes 8 levels
+    # two checks
+    assert lv(_levels(8), 9, H=5, W=5) == INVALID                    # L, H * W
+    assert lv(good, 2, H=5, W=5, M=0) == UNSUPPORTED                 # H * W, no work
+    assert lv(_levels(2, H2=0), 2, M=0) == OK                        # level, no work
+    assert lv(_levels(2, H2=0), 2, H=5, W=5) == UNSUPPORTED          # level, H * W
+    assert lv(_levels(2, scale=-1.0), 2, dtype=2) == INVALID         # level, dtype
+    assert lv(good, 2, dtype=2, M=0) == OK                           # dtype, no work
+    assert lv(good, 2, dtype=2, H=5, W=5) == UNSUPPORTED
+
+    # ---- dpvo_corr_forward_levels_nhwc[_ordered]: the same arguments (+ order before B)
+    def entries():
+        g = lib.dpvo_corr_forward_levels_nhwc
+
+        def plain(ptrs, arrs, L, B=1, M=4, C=128, H=3, W=3, R=3, dtype=0, out=one):
+            f1, co, ii, jj = ptrs
+            return g(f1, *arrs, L, co, ii, jj, B, M, C, H, W, 9, 4, R, dtype, out, None)
+
+        h = lib.dpvo_corr_forward_levels_nhwc_ordered
+
+        def ordered(ptrs, arrs, L, B=1, M=4, C=128, H=3, W=3, R=3, dtype=0, out=one):
+            f1, co, ii, jj = ptrs
+            return h(f1, *arrs, L, co, ii, jj, one, B, M, C, H, W, 9, 4, R, dtype, out, None)
+
+        return plain, ordered
+
+    p4 = (one,) * 4
+    for nh in entries():
+        assert nh(p4, good, 0) == INVALID and nh(p4, good, -2) == INVALID
+        assert nh(p4, good, 2, R=-1) == INVALID and nh(p4, good, 2, R=8) == INVALID
+        assert nh(p4, good, 2, C=0) == INVALID and nh(p4, good, 2, H=0) == INVALID
+        assert nh(p4, good, 2, W=0) == INVALID
+        for k in range(4):  # each null input with work to do
+            assert nh(p4[:k] + (None,) + p4[k + 1:], good, 2) == INVALID
+        assert nh(p4, good, 2, out=None) == INVALID
+        for bad in (dict(fmap2=None), dict(H2=0), dict(W2=-3), dict(scale=0.0), dict(scale=nan)):
+            assert nh(p4, _levels(2, at=1, **bad), 2) == INVALID
+        assert nh(p4, good, 2, dtype=2) == UNSUPPORTED and nh(p4, good, 2, dtype=7) == UNSUPPORTED
+        assert nh(p4, good, 2, C=64) == UNSUPPORTED
+        assert nh(p4, _levels(5), 5) == UNSUPPORTED                  # L > 4
+        assert nh(p4, good, 2, H=5, W=4) == UNSUPPORTED              # H * W > 16
+        assert nh(p4, good, 2, R=4) == UNSUPPORTED                   # 81 * 9 outputs > 512
+        assert nh(p4, good, 2, H=1, W=1, R=6) == UNSUPPORTED         # D * D = 196 > 164
+        assert nh(p4, good, 2, M=0) == OK and nh(p4, good, 2, B=0) == OK
+        assert nh(p4, good, 2, M=0, dtype=1) == OK
+        # two checks
+        assert nh(p4, good, 0, C=64) == INVALID                      # L, C
+        assert nh(p4, good, 2, C=64, M=0) == UNSUPPORTED             # C, no work
+        assert nh(p4, _levels(2, H2=0), 2, M=0) == OK                # level, no work
+        assert nh(p4, _levels(2, H2=0), 2, C=64) == UNSUPPORTED      # level, C
+        assert nh(p4, _levels(2, H2=0), 2, H=1, W=1, R=6) == INVALID     # level, D * D
+        assert nh(p4, good, 2, H=1, W=1, R=6, M=0) == OK             # D * D, no work
+        assert nh(p4, _levels(8), 9, R=8) == INVALID                 # radius, L
+
+    # ---- dpvo_corr_backward: .., jj, grad, B, M, C, H, W, N1, N2, H2, W2, radius, dtype, g1, g2
+    # (rows rejected ahead of the memset of the gradients only)
+    f = lib.dpvo_corr_backward
+    p6 = (one,) * 6
+    for B, M, C, H, W, R in ((-1, 4, 128, 3, 3, 3), (1, -4, 128, 3, 3, 3), (1, 4, 0, 3, 3, 3),
+                             (1, 4, 128, 0, 3, 3), (1, 4, 128, 3, 0, 3), (1, 4, 128, 3, 3, -1),
+                             (1, 4, 128, 3, 3, 8)):
+        assert f(*p6, B, M, C, H, W, 9, 4, 8, 8, R, 0, one, one, None) == INVALID
+    assert f(*p6, 1, 4, 128, 5, 4, 9, 4, 8, 8, 3, 0, one, one, None) == UNSUPPORTED
+    assert f(*p6, 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 1, one, one, None) == UNSUPPORTED  # fp16
+    assert f(*p6, 1, 4, 128, 3, 3, 9, 4, 8, 8, 3, 2, one, one, None) == UNSUPPORTED  # fp64
+    assert f(*p6, 1, 4, 128, 5, 5, 9, 4, 8, 8, 8, 0, one, one, None) == INVALID      # radius, H * W
+    assert f(*p6, 1, 4, 0, 3, 3, 9, 4, 8, 8, 3, 1, one, one, None) == INVALID        # C, dtype
+    assert f(*p6, 1, 0, 128, 5, 5, 9, 4, 8, 8, 3, 1, one, one, None) == UNSUPPORTED
+
+    # ---- dpvo_patchify_forward: net, coords, B, C, H, W, M, radius, clamp, dtype, out
+    f = lib.dpvo_patchify_forward
+    for B, C, H, W, M, R in ((-1, 8, 6, 6, 4, 3), (1, 0, 6, 6, 4, 3), (1, 8, 0, 6, 4, 3),
+                             (1, 8, 6, 0, 4, 3), (1, 8, 6, 6, -4, 3), (1, 8, 6, 6, 4, -1)):
+        assert f(one, one, B, C, H, W, M, R, 0, 0, one, None) == INVALID
+    assert f(one, one, 1, 8, 6, 6, 4, 3, 0, 7, one, None) == INVALID      # unknown dtype
+    assert f(one, one, 0, 8, 6, 6, 4, 3, 0, 0, one, None) == OK
+    assert f(one, one, 1, 8, 6, 6, 0, 3, 1, 2, one, None) == OK
+    assert f(one, one, 1, 8, 6, 6, 0, 3, 0, 7, one, None) == OK           # dtype, no work
+    assert f(one, one, 1, 0, 6, 6, 0, 3, 0, 7, one, None) == INVALID      # C, no work
+    # ---- dpvo_patchify_backward: grad, coords, .., net_grad (rows ahead of the memset only)
+    f = lib.dpvo_patchify_backward
+    for B, C, H, W, M, R in ((-1, 8, 6, 6, 4, 3), (1, 0, 6, 6, 4, 3), (1, 8, 0, 6, 4, 3),
+                             (1, 8, 6, 0, 4, 3), (1, 8, 6, 6, -4, 3), (1, 8, 6, 6, 4, -1)):
+        assert f(one, one, B, C, H, W, M, R, 0, 0, one, None) == INVALID
+    assert f(one, one, 1, 8, 6, 6, 4, 3, 0, 1, one, None) == UNSUPPORTED
+    assert f(one, one, 1, 8, 6, 6, 4, 3, 0, 2, one, None) == UNSUPPORTED
+    assert f(one, one, 1, 0, 6, 6, 4, 3, 0, 1, one, None) == INVALID      # C, dtype
+    assert f(one, one, 1, 8, 6, 6, 0, 3, 0, 1, one, None) == UNSUPPORTED  # dtype, no work
+
+    # ---- dpvo_feature_to_nhwc: src, dst, count, C, H, W, dtype
+    f = lib.dpvo_feature_to_nhwc
+    for count, C, H, W in ((-1, 8, 6, 6), (2, 0, 6, 6), (2, 8, 0, 6), (2, 8, 6, 0)):
+        assert f(one, one, count, C, H, W, 0, None) == INVALID
+    assert f(None, one, 2, 8, 6, 6, 0, None) == INVALID and f(one, None, 2, 8, 6, 6, 0, None) == INVALID
+    assert f(one, one, 2, 8, 6, 6, 2, None) == UNSUPPORTED and f(one, one, 2, 8, 6, 6, 7, None) == UNSUPPORTED
+    assert f(one, one, 0, 8, 6, 6, 0, None) == OK
+    assert f(one, one, 0, 8, 6, 6, 2, None) == OK          # dtype, no work
+    assert f(None, one, 0, 8, 6, 6, 0, None) == INVALID    # null, no work
+    assert f(None, one, 2, 8, 6, 6, 2, None) == INVALID    # null, dtype
+
+    # ---- dpvo_feature_pyramid_insert: src, dst[], scale[], L, C, H, W, dtype
+    f = lib.dpvo_feature_pyramid_insert
+    VP, I4, I8 = ctypes.c_void_p * 2, ctypes.c_int * 2, ctypes.c_int64 * 2
+    dst, scale = VP(1, 1), I4(1, 4)
+    assert f(None, dst, scale, 2, 64, 32, 32, 0, None) == INVALID
+    assert f(one, None, scale, 2, 64, 32, 32, 0, None) == INVALID
+    assert f(one, dst, None, 2, 64, 32, 32, 0, None) == INVALID
+    assert f(one, dst, scale, 0, 64, 32, 32, 0, None) == INVALID
+    for C, H, W in ((0, 32, 32), (64, 0, 32), (64, 32, 0)):
+        assert f(one, dst, scale, 2, C, H, W, 0, None) == INVALID
+    assert f(one, VP(1, None), scale, 2, 64, 32, 32, 1, None) == INVALID
+    assert f(one, dst, scale, 2, 64, 32, 32, 2, None) == UNSUPPORTED      # fp64 pyramid
+    assert f(one, dst, scale, 5, 64, 32, 32, 0, None) == UNSUPPORTED      # L > 4
+    assert f(one, dst, I4(1, 3), 2, 64, 32, 32, 0, None) == UNSUPPORTED
+    assert f(one, dst, I4(16, 1), 2, 64, 32, 32, 1, None) == UNSUPPORTED
+    assert f(one, dst, scale, 0, 64, 32, 32, 2, None) == INVALID              # L, dtype
+    assert f(one, VP(1, None), scale, 2, 64, 32, 32, 2, None) == UNSUPPORTED  # dtype, null level
+    assert f(one, VP(None, 1), I4(1, 3), 2, 64, 32, 32, 0, None) == INVALID   # level 0 first
+    assert f(one, VP(1, None), I4(3, 1), 2, 64, 32, 32, 0, None) == UNSUPPORTED
+    # ---- dpvo_feature_pyramid_insert_ring: src, dst0[], slot_bytes[], scale[], L, C, H, W, mem,
+    #      slot_dev, dtype
+    f = lib.dpvo_feature_pyramid_insert_ring
+    sb = I8(1 << 20, 1 << 16)
+    assert f(one, dst, sb, scale, 2, 64, 32, 32, 8, None, 0, None) == INVALID   # slot_dev
+    assert f(one, dst, sb, scale, 2, 64, 32, 32, 0, one, 0, None) == INVALID    # mem
+    assert f(one, dst, None, scale, 2, 64, 32, 32, 8, one, 0, None) == INVALID  # slot_bytes
+    assert f(None, dst, sb, scale, 2, 64, 32, 32, 8, one, 0, None) == INVALID
+    assert f(one, dst, sb, scale, 0, 64, 32, 32, 8, one, 0, None) == INVALID
+    assert f(one, VP(1, None), sb, scale, 2, 64, 32, 32, 8, one, 0, None) == INVALID
+    assert f(one, dst, sb, scale, 2, 64, 32, 32, 8, one, 2, None) == UNSUPPORTED
+    assert f(one, dst, sb, scale, 5, 64, 32, 32, 8, one, 1, None) == UNSUPPORTED
+    assert f(one, dst, sb, I4(1, 5), 2, 64, 32, 32, 8, one, 0, None) == UNSUPPORTED
+    assert f(one, dst, sb, scale, 2, 64, 32, 32, 8, None, 2, None) == INVALID       # slot_dev, dtype
+    assert f(one, dst, sb, scale, 2, 64, 32, 32, 0, one, 2, None) == UNSUPPORTED    # mem, dtype
+    assert f(one, dst, None, I4(1, 3), 2, 64, 32, 32, 8, one, 0, None) == INVALID   # slot_bytes, scale
+
+    # ==== The rows below differ from the build before the refactor: the checks
+    # ==== it added (dpvo_corr_forward_levels and the channels-last entries now
+    # ==== look at B, M and every pointer first), and the new query export.
+    if not hasattr(lib, "dpvo_corr_query_path"):
+        pytest.fail("dpvo_corr_query_path is not exported")
+    f = lib.dpvo_corr_forward_levels
+    assert lv(good, 2, B=-1) == INVALID and lv(good, 2, M=-4) == INVALID
+    assert lv(good, 2, B=-1, M=-4) == INVALID                        # B * M > 0 reached the launch
+    for k in range(4):  # fmap2 / H2 / W2 / scale arrays
+        assert lv(good[:k] + (None,) + good[k + 1:], 2) == INVALID
+        assert lv(good[:k] + (None,) + good[k + 1:], 2, M=0) == INVALID
+    for k in (0, 6, 7, 8, 18):  # fmap1, coords, ii, jj, out
+        a = [one, *good, 2, one, one, one, 1, 4, 128, 3, 3, 9, 4, 3, 0, one, None]
+        a[k] = None
+        assert f(*a) == INVALID
+        a[10] = 0  # M
+        assert f(*a) == INVALID
+        a[12], a[13] = 5, 5
+        assert f(*a) == INVALID                                      # null before H * W
+    for nh in entries():
+        assert nh(p4, good, 2, B=-1) == INVALID and nh(p4, good, 2, M=-4) == INVALID
+        for k in range(4):
+            arrs = good[:k] + (None,) + good[k + 1:]
+            assert nh(p4, arrs, 2) == INVALID and nh(p4, arrs, 2, M=0) == INVALID
+            ptrs = p4[:k] + (None,) + p4[k + 1:]
+            assert nh(ptrs, good, 2, M=0) == INVALID
+            assert nh(ptrs, good, 2, C=64) == INVALID                # null before the envelope
+        assert nh(p4, good, 2, M=0, out=None) == INVALID
+    # dpvo_corr_query_path: entry, then the ordered entry's arguments without stream; path out
+    q = lib.dpvo_corr_query_path
+    path = ctypes.c_int(-1)
+
+    def query(entry, arrs, L, B=1, M=4, C=128, H=3, W=3, N2=4, R=3, dtype=0, f1=16):
+        path.value = -1
+        st = q(entry, ctypes.c_void_p(f1), *arrs, L, one, one, one, None, B, M, C, H, W, 9, N2, R,
+               dtype, one, ctypes.byref(path))
+        return st, path.value
+
+    NONE, NHWC, MMA, MMA_ORDERED, VALU = range(5)
+    al = _levels(2, fmap2=16)
+    al[0][1] = 16
+    assert query(0, al, 1) == (OK, MMA) and query(1, al, 2) == (OK, MMA)
+    assert query(2, al, 2) == (OK, NHWC)
+    assert query(0, al, 1, C=64) == (OK, VALU) and query(1, al, 2, f1=8) == (OK, VALU)
+    assert query(0, al, 1, dtype=2) == (OK, VALU)
+    assert query(1, al, 2, dtype=2) == (UNSUPPORTED, NONE)
+    assert query(0, al, 1, dtype=7) == (INVALID, NONE)
+    assert query(2, al, 2, C=64) == (UNSUPPORTED, NONE)
+    assert query(1, al, 2, M=0) == (OK, NONE)
+    assert query(3, al, 2) == (INVALID, NONE)                        # no such entry
+    assert q(1, one, *al, 2, one, one, one, None, 1, 4, 128, 3, 3, 9, 4, 3, 0, one, None) == INVALID
+    big = _levels(1, fmap2=16, H2=128, W2=128)                       # 1100 x 128 x 128^2 x 4 B
+    assert query(1, big, 1, N2=1100) == (OK, MMA_ORDERED)
+    assert query(1, big, 1, N2=1100, B=2) == (OK, MMA)
+
+
 def test_workspace_size_grows_with_problem(lib):
     a = lib.dpvo_ba_workspace_bytes(256, 1, 8)
     b = lib.dpvo_ba_workspace_bytes(2048, 1, 12)

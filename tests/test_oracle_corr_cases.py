@@ -3,6 +3,9 @@ and the box arithmetic of the three A-CORR forward kernels; here hand-made
 inputs pin that restatement, and every case of the tables that
 test_corr_dispatch_gpu.py runs is shown to reach the branch it is named for
 (the conditions are on the chosen seeds, so they are checked, not assumed)."""
+import ctypes
+import inspect
+
 import numpy as np
 import pytest
 import torch
@@ -229,6 +232,111 @@ def test_e_threshold_ring_is_the_fp16_one():
     assert C.E_RINGS[F16]["N2"] == C.kOrdMaxN2
     s = C.E_RINGS[F16]
     assert not C.nchw_ordered(1, 1030, s["N2"] + 1, [(s["H2"], s["W2"])], F16)
+
+
+# ------------------------------------- the restatement pinned to the native code
+FORWARD, LEVELS, LEVELS_NHWC = 0, 1, 2                  # dpvo_hot.h: DPVO_CORR_*
+NONE, NHWC, NCHW_MMA, NCHW_MMA_ORDERED, VALU = range(5)  # DPVO_CORR_PATH_*
+_CASE_DEFAULTS = {k: v.default for k, v in inspect.signature(_case).parameters.items()
+                  if v.default is not inspect.Parameter.empty}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import dpvo_amd
+
+    return dpvo_amd.c_abi()
+
+
+def _query(lib, entry, hp, wp, R, Cc, shapes, dtype, B, M, N2, align=16, f1=16):
+    """dpvo_corr_query_path on a call of these sizes; fmap1 is the address
+    `f1`, every level `align` (the tables' tensors are torch allocations: 16-B
+    aligned)."""
+    L = len(shapes)
+    p = ctypes.c_void_p(f1)
+    f2 = (ctypes.c_void_p * L)(*[align] * L)
+    H2 = (ctypes.c_int * L)(*[h for h, _ in shapes])
+    W2 = (ctypes.c_int * L)(*[w for _, w in shapes])
+    sc = (ctypes.c_float * L)(*[1.0] * L)
+    path = ctypes.c_int(-1)
+    st = lib.dpvo_corr_query_path(entry, p, f2, H2, W2, sc, L, p, p, p, None, B, M, Cc, hp, wp, 9,
+                                  N2, R, {F32: 0, F16: 1}[dtype], p, ctypes.byref(path))
+    return st, path.value
+
+
+def _pin(lib, hp, wp, R, Cc, shapes, dtype, B, M, N2, single=False):
+    """The native selection of one call against nhwc_refusals / nhwc_supported,
+    nchw_mma_supported and nchw_ordered; returns the path of the call sequence
+    of the extension for a channels-last and for an NCHW pyramid."""
+    L = len(shapes)
+    why = C.nhwc_refusals(hp, wp, R, Cc, L, dtype)
+    assert C.nhwc_supported(hp, wp, R, Cc, L, dtype) == (not why)
+    assert _query(lib, LEVELS_NHWC, hp, wp, R, Cc, shapes, dtype, B, M, N2) == \
+        ((3, NONE) if why else (0, NHWC)), why
+    want = VALU
+    if C.nchw_mma_supported(hp, wp, R, Cc, L, shapes, dtype):
+        want = NCHW_MMA_ORDERED if C.nchw_ordered(B, M, N2, shapes, dtype) else NCHW_MMA
+    assert _query(lib, LEVELS, hp, wp, R, Cc, shapes, dtype, B, M, N2) == (0, want)
+    if single:
+        assert L == 1
+        assert _query(lib, FORWARD, hp, wp, R, Cc, shapes, dtype, B, M, N2) == (0, want)
+    return (want if why else NHWC), want
+
+
+def _pin_case(lib, kw, levels, dtype, **over):
+    d = dict(_CASE_DEFAULTS, **kw)
+    d.update(over)
+    hp, wp = d["Hp"] or d["p"], d["Wp"] or d["p"]
+    return _pin(lib, hp, wp, d["R"], d["C"], C.level_shapes(d["H2"], d["W2"], levels), dtype,
+                d["B"], d["M"], d["N2"])
+
+
+@pytest.mark.parametrize("dtype", C.DTYPES, ids=["f32", "f16"])
+def test_tables_select_what_the_restatement_predicts(lib, dtype):
+    """Every case of the A .. F tables, and the two threshold cases of
+    test_corr_dispatch_gpu.py, through dpvo_corr_query_path."""
+    for _, kw, levels, _ in C.a_cases():
+        assert _pin_case(lib, kw, levels, dtype)[0] == NHWC
+    for p, R, _ in C.B_SHAPES:
+        for L in (1, 2, 3, 4):
+            for B, M in C.B_UNORDERED + [(1, m) for m in C.B_ORDERED_M]:
+                assert _pin_case(lib, dict(B=B, M=M, p=p, R=R), C.SCALES[:L], dtype)[0] == NHWC
+    for name, kw, levels, why in C.C_CASES:
+        cl, nchw = _pin_case(lib, kw, levels, dtype)
+        assert (cl == NHWC) == (not why)
+        # what the NCHW entry then runs: C = 64 and five levels are past the matrix cores too
+        assert nchw == (VALU if why & {"C", "L"} else NCHW_MMA), name
+    for name, kw, levels, dt in C.D_CASES:  # pinned for both dtypes, VALU for the case's own
+        assert _pin_case(lib, kw, levels, dtype)[1] == VALU or dt != dtype, name
+    s = C.E_RINGS[dtype]
+    shape = [(s["H2"], s["W2"])]
+    for M in C.E_M + [5, 257]:
+        assert _pin(lib, 3, 3, 3, 128, shape, dtype, 1, M, s["N2"], single=True)[1] == \
+            NCHW_MMA_ORDERED
+        assert _pin(lib, 3, 3, 3, 128, shape * 2, dtype, 1, M, s["N2"])[1] == NCHW_MMA_ORDERED
+    for kernel, spec in C.F_KERNELS.items():
+        for levels in C.F_LEVELS:
+            cl, nchw = _pin_case(lib, dict(M=67, C=spec["C"]), levels, dtype)
+            got = cl if spec["layout"] == "cl" else nchw
+            assert got == {"nhwc": NHWC, "nchw_mma": NCHW_MMA, "valu": VALU}[kernel]
+    # test_nchw_ordered_edge_count_threshold (fp32 ring) / _frame_count_threshold (fp16 ring)
+    s = C.E_RINGS[F32]
+    for M, want in ((C.kOrdMaxE, NCHW_MMA_ORDERED), (C.kOrdMaxE + 1, NCHW_MMA)):
+        assert _pin(lib, 3, 3, 3, 128, [(s["H2"], s["W2"])], F32, 1, M, s["N2"], True)[1] == want
+    s = C.E_RINGS[F16]
+    for N2, want in ((C.kOrdMaxN2, NCHW_MMA_ORDERED), (C.kOrdMaxN2 + 1, NCHW_MMA)):
+        assert _pin(lib, 3, 3, 3, 128, [(s["H2"], s["W2"])], F16, 1, 1030, N2, True)[1] == want
+
+
+def test_alignment_the_restatement_assumes(lib):
+    """nchw_mma_supported is stated for 16-B aligned bases: an 8-B aligned level
+    still takes the matrix cores (8-B pieces), a 4-B aligned one or an fmap1
+    off 16 B the VALU kernel."""
+    args = (3, 3, 3, 128, [(24, 32)], F32, 1, 37, 4)
+    assert _query(lib, LEVELS, *args, align=16) == (0, NCHW_MMA)
+    assert _query(lib, LEVELS, *args, align=8) == (0, NCHW_MMA)
+    assert _query(lib, LEVELS, *args, align=4) == (0, VALU)
+    assert _query(lib, LEVELS, *args, f1=8) == (0, VALU)
 
 
 @pytest.mark.parametrize("levels", C.F_LEVELS, ids=["L1", "L4"])
