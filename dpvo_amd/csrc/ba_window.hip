@@ -92,6 +92,7 @@ struct Plan {          // written by ba_plan_kernel, read by ba_window_kernel
   int* poff;           // [E + 1] first position of patch u
   unsigned* pmask;     // [E] free-pose bitmask of patch u
   int* pkk;            // [E] patch id (kk) of patch u
+  unsigned short* pslot;  // [E] pose slots of the edge at position p: wslot(ii) | wslot(jj) << 8
   int* meta;           // [kMetaBytes / 4]: nuniq, fmin, status, shards, stamps, block work
   int* status;         // the workspace status word, reset here
   int* sink;           // caller's sticky status word or null
@@ -141,6 +142,23 @@ __device__ __forceinline__ void mark(const WArgs& A, int slot) {
   if (A.marks && blockIdx.x == 0 && threadIdx.x == 0) A.marks[slot] = (int64_t)wall_clock64();
 }
 
+
+// LDS pose-table slot of global pose gp: free poses [t0, t0 + N) first, then
+// the fixed poses from fmin (the smallest one); kHbm past the table
+__device__ __forceinline__ unsigned wslot(int gp, int t0, int N, int fmin) {
+  if (gp >= t0 && gp < t0 + N) return (unsigned)(gp - t0);
+  const int k = gp - fmin;
+  return (k >= 0 && k < kWSlots - N) ? (unsigned)(N + k) : kHbm;
+}
+// the slot pair of an edge as the window kernel keeps it (WL::ec)
+__device__ __forceinline__ unsigned short pslot_of(int gi, int gj, int t0, int N, int fmin) {
+  return (unsigned short)(wslot(gi, t0, N, fmin) | (wslot(gj, t0, N, fmin) << 8));
+}
+// (int)x[e] of an int64 array, as the window kernel narrowed the pose ids it read:
+// the low word alone
+__device__ __forceinline__ int low_word(const int64_t* x, int e) {
+  return reinterpret_cast<const int*>(x)[2 * (size_t)e];
+}
 
 // ===========================================================================
 // plan: group edges by patch (one workgroup, 512 threads)
@@ -331,10 +349,12 @@ __device__ __forceinline__ void plan_block(const int64_t* __restrict__ ii,
     for (int r = 0; r < kPlanPer; r++) {
       const int e = tid + r * T;
       if (e >= E) continue;
+      const int gi = low_word(ii, e), gj = low_word(jj, e);  // (L2 hits, under the rank's LDS reads)
       const int v = kv[r] - kmin, hv = hist[v];
       const int b = hv >> 14, a = (v == 0) ? 0 : (hist[v - 1] >> 14);
       const int rank = bucket_rank(spos, a, b, e);
       plan.epos[a + rank] = e;
+      plan.pslot[a + rank] = pslot_of(gi, gj, t0, N, ctl[2]);
       if (rank == 0) {
         const int u = hv & 0x3fff;
         plan.poff[u] = a;
@@ -472,6 +492,7 @@ __device__ __forceinline__ void plan_block(const int64_t* __restrict__ ii,
     const int u = u1 - 1;                            // patch of position p
     const int e = pos_edge[p];
     plan.epos[p] = e;
+    plan.pslot[p] = pslot_of(low_word(ii, e), low_word(jj, e), t0, N, ctl[2]);
     if (is_head) {
       plan.poff[u] = p;
       plan.pkk[u] = (int)min(max(kk[e], (int64_t)0), (int64_t)kmaxc);
@@ -686,6 +707,11 @@ __device__ __forceinline__ void plan_sharded_k(const int64_t* __restrict__ ii,
   lds_barrier();
   stamp(4);
   // hf[bucket] >> 14 is now the END of the bucket; the patch index is unchanged.
+  // The poses of the edge at this thread's first position, for its slot pair
+  // (L2 hits: the pass above read them): issued here, so that the round trip
+  // runs under the block work.  Index clamped: the load stays unconditional.
+  const int e_first = min((int)spos[min(below + tid, cap - 1)], E - 1);
+  int gi = low_word(ii, e_first), gj = low_word(jj, e_first);
   // block work of the local patches
   plan_block_work(nl, [&](int v, int& c, unsigned& m) {
     c = (hf[(kmin + lo + v) & zm] >> 14) - (v == 0 ? below : (hf[(kmin + lo + v - 1) & zm] >> 14));
@@ -696,10 +722,15 @@ __device__ __forceinline__ void plan_sharded_k(const int64_t* __restrict__ ii,
   // E / S of them) ranks its edge among the bucket's members
   for (int p = below + tid; p < top; p += T) {
     const int e = spos[p], v = sv[p];
+    if (p != below + tid) {
+      gi = low_word(ii, e);
+      gj = low_word(jj, e);
+    }
     const int hv = hf[(kmin + lo + v) & zm];
     const int b = hv >> 14, a = v == 0 ? below : (hf[(kmin + lo + v - 1) & zm] >> 14);
     const int rank = bucket_rank(spos, a, b, e);
     plan.epos[a + rank] = e;
+    plan.pslot[a + rank] = pslot_of(gi, gj, t0, N, ctl[2]);
     if (rank == 0) {
       const int u = hv & 0x3fff;
       plan.poff[u] = a;
@@ -969,12 +1000,6 @@ __device__ __forceinline__ double edges_etdx(const WL& L, const WArgs& A, int q0
 }
 __device__ __forceinline__ double patch_etdx(const WL& L, const WArgs& A, int ri, int par, int N) {
   return edges_etdx(L, A, L.roff[ri], L.roff[ri + 1], par, N);
-}
-
-__device__ __forceinline__ unsigned wslot(int gp, int t0, int N, int fmin) {
-  if (gp >= t0 && gp < t0 + N) return (unsigned)(gp - t0);
-  const int k = gp - fmin;
-  return (k >= 0 && k < kWSlots - N) ? (unsigned)(N + k) : kHbm;
 }
 
 __device__ __forceinline__ void pose_of(const WArgs& A, const WL& L, unsigned slot, int gp,
@@ -1328,6 +1353,16 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
     pb0[r] = A.plan.poff[u + 1];
     kx0[r] = A.plan.pkk[u];
   }
+  // ... and so do the free-pose rows of the pose table, which need t0 only
+  // (every slot loads the row it would hold as a free pose; the fixed-pose
+  // rows need fmin and go out with the second batch)
+  constexpr int kPr = kWSlots * 8 / kWT;
+  float pvf[kPr];
+#pragma unroll
+  for (int r = 0; r < kPr; r++) {
+    const int k = tid + r * kWT, sl = k >> 3, c = k & 7;
+    pvf[r] = A.poses[7 * (size_t)min(max(t0w + sl, 0), A.num_poses - 1) + min(c, 6)];
+  }
   const int nuniq = A.plan.meta[0], fmin = A.plan.meta[1];
   // ---------------- workgroups -> lower blocks ----------------
   // Blocks in the order diagonal (j < N: (j, j)) then strictly lower
@@ -1435,13 +1470,19 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   auto diag_shares = [&](int p) { return bstart[p + 1] - bstart[p]; };
   // ---------------- setup: relevant patches of this workgroup ----------------
   // rel(u): mask holds a and b and u % S == sub; workgroup 0 also takes the
-  // patches without a free pose (their dZ = Q u).  One scan packs
-  // (#patches << 16 | #edges) (E <= 4096 keeps both below 2^16).
+  // patches without a free pose (their dZ = Q u).  Record index and first
+  // relevant edge of a patch are one packed count (#patches << 16 | #edges,
+  // both <= kWMaxE < 2^16) prefixed in ascending patch order u = tid + r kWT:
+  // a DPP scan inside the wave per slot r, then the (slot, wave) totals -- 32
+  // ints per kB * 256 patches -- through LDS and one barrier.  No pass over
+  // all nuniq patches: a workgroup keeps about 1 % of them.
   // Global round trips are the setup's cost (~1 us each on a cold L2): the
-  // plan meta and the first kB * 256 patches' plan entries are loaded in ONE
-  // batch (speculatively, indices clamped to the E-sized arrays), then the
-  // patch values, the edge ids and the pose table in a second, then the
-  // per-edge inputs in a third.
+  // plan meta, the first kB * 256 patches' plan entries (speculatively,
+  // indices clamped to the E-sized arrays) and the free-pose rows are loaded
+  // in ONE batch; the patch values, then -- behind an LDS-only barrier, so
+  // still in the same flight -- the edge ids and slot pairs of the
+  // workgroup's sorted positions and the fixed-pose rows in a second; target
+  // and weight by edge id in a third.
   const unsigned need = (NB > 0) ? ((1u << a) | (1u << b)) : 0u;
   if (tid == 0) {
     ctl[cFail] = 0;
@@ -1450,31 +1491,49 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
     ctl[cCap] = 0;
     ctl[cLMulti] = 0;
   }
-  int* cnt = (int*)(lds + off);  // [nuniq] scan input / prefix (kept until the records are built)
+  static_assert(kWT == 256 && kB * (kWT / 64) == 32 && cScan + 32 <= 64,
+                "the first batch's (slot, wave) totals fill ctl[cScan, cScan + 32)");
+  constexpr int kBatch = kB * kWT, kTot = kB * (kWT / 64);
+  constexpr int kXBatch = (kWMaxE + kBatch - 1) / kBatch - 1;  // batches past the first
+  // past the first batch (nuniq > kB * 256): the totals of every further batch,
+  // then each patch's prefix inside its wave (kept until the records are built)
+  int* wtx = (int*)(lds + off);   // [kXBatch][kTot]
+  int* xs = wtx + kXBatch * kTot;  // [nuniq - kBatch]
+  static_assert(kXBatch * kTot <= kBatch, "wtx + xs lie inside the nuniq + 1 ints before the records");
+  const int lane_s = tid & 63, wid_s = tid >> 6;
   auto relevant = [&](unsigned m, int u) {
     return (NB == 0) ? true : (((m & need) == need && (u % S) == sub) || (g == 0 && m == 0));
   };
+  int x0[kB];         // packed count of the relevant patches before this one in its (slot, wave)
+  unsigned relb = 0;  // bit r: patch tid + r kWT is relevant
 #pragma unroll
   for (int r = 0; r < kB; r++) {
     const int u = tid + r * kWT;
-    if (u < nuniq) cnt[u] = relevant(m0[r], u) ? ((1 << 16) | (pb0[r] - pa0[r])) : 0;
+    const int cv = (u < nuniq && relevant(m0[r], u)) ? ((1 << 16) | (pb0[r] - pa0[r])) : 0;
+    const int incl = wave_incl_sum(cv);
+    x0[r] = incl - cv;
+    relb |= cv ? (1u << r) : 0u;
+    if (lane_s == 63) scr[r * (kWT / 64) + wid_s] = incl;
   }
-  // patches past the first batch (nuniq > kB * 256): loaded here, kB per thread
-  // per round trip (loads unconditional: index clamped, value selected after)
-  for (int u0 = tid + kB * kWT; u0 < nuniq; u0 += kB * kWT) {
+  // patches past the first batch: loaded here, kB per thread per round trip
+  // (loads unconditional: index clamped, value selected after)
+  for (int ub = kBatch, bx = 0; ub < nuniq; ub += kBatch, bx++) {  // block-uniform
     unsigned m[kB];
     int p0[kB], p1[kB];
 #pragma unroll
     for (int r = 0; r < kB; r++) {
-      const int u = min(u0 + r * kWT, nuniq - 1);
+      const int u = min(ub + tid + r * kWT, nuniq - 1);
       m[r] = A.plan.pmask[u];
       p0[r] = A.plan.poff[u];
       p1[r] = A.plan.poff[u + 1];
     }
 #pragma unroll
     for (int r = 0; r < kB; r++) {
-      const int u = u0 + r * kWT;
-      if (u < nuniq) cnt[u] = relevant(m[r], u) ? ((1 << 16) | (p1[r] - p0[r])) : 0;
+      const int u = ub + tid + r * kWT;
+      const int cv = (u < nuniq && relevant(m[r], u)) ? ((1 << 16) | (p1[r] - p0[r])) : 0;
+      const int incl = wave_incl_sum(cv);
+      if (u < nuniq) xs[u - kBatch] = incl - cv;
+      if (lane_s == 63) wtx[bx * kTot + r * (kWT / 64) + wid_s] = incl;
     }
   }
   mark(A, 40);
@@ -1488,10 +1547,27 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
     else if (s1 - s0 > 1)
       mlist[atomicAdd(&ctl[cLMulti], 1)] = o | ((o + aa) << 16);  // any order: sums are per block
   }
-  const int tot = fscan(cnt, nuniq, scr);
+  // the prefix of the (slot, wave) totals in patch order, by every thread for
+  // itself: base0[r] = packed count before this wave's part of slot r
+  int base0[kB], tot = 0;
+#pragma unroll
+  for (int r = 0; r < kB; r++) {
+    const int4 w4 = *reinterpret_cast<const int4*>(scr + r * (kWT / 64));
+    const int w[4] = {w4.x, w4.y, w4.z, w4.w};
+    base0[r] = tot;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      base0[r] += k < wid_s ? w[k] : 0;
+      tot += w[k];
+    }
+  }
+  const int tot1 = tot;  // the first batch's share
+  for (int ub = kBatch, bx = 0; ub < nuniq; ub += kBatch, bx++)
+    for (int k = 0; k < kTot; k++) tot += wtx[bx * kTot + k];
   mark(A, 41);
   int nrel = tot >> 16, nrp = tot & 0xffff;
-  // LDS plan: [head | cnt | patch records | edge records | region | tw | ej]
+  // LDS plan: [head | nuniq + 1 ints (wtx, xs past the first batch) | patch records |
+  //            edge records | region | tw | ej]
   const size_t chunk_b = sizeof(double) * 2 * 14 * kChunk;  // edge records + per-patch sums
   const size_t red_b = sizeof(double) * (36 * 128 + 36 * 8);
   const size_t NN = N > 0 ? N : 1;
@@ -1544,8 +1620,7 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   // pass A1, thread per relevant patch, no global loads: record offsets, the
   // patch of every position, the final-depth writer
   int* rpo = reinterpret_cast<int*>(L.qu);  // first sorted position (until the first linearisation)
-  auto record = [&](int u, int kx, int po, unsigned m, int c0, int c1) {
-    const int ri = c0 >> 16, q0 = c0 & 0xffff, ne = (c1 - c0) & 0xffff;
+  auto record = [&](int ri, int u, int kx, int po, unsigned m, int q0, int ne) {
     L.roff[ri] = q0;
     rpo[ri] = po;
     for (int t = 0; t < ne; t++) L.rp[q0 + t] = (unsigned short)ri;
@@ -1576,126 +1651,139 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   // workgroup's few relevant patches are scattered over the kB slots of all
   // threads, so record() run per slot issued its ~200 instructions kB times
   // per wave; per record index it runs once.
-  auto cnt_at = [&](int u) { return (u < nuniq) ? cnt[u] : tot; };
   static_assert(kWMaxE <= 65536 && kWMaxN <= 16, "patch index and pose mask packed in 16 bits each");
   int* dl = rpo + (nrel + 1);  // [nrel][3] scratch in qu's space past rpo (qu: 4 ints per record)
-  bool lv0[kB];
-  {
-    int c0[kB], c1[kB];
+  int2* dq = reinterpret_cast<int2*>(L.nxy);  // [nrel] (first relevant edge, edges) until nxy is written
+  if (nrel > 0) {
 #pragma unroll
     for (int r = 0; r < kB; r++) {
-      const int u = min(tid + r * kWT, nuniq - 1);
-      c0[r] = cnt[u];
-      c1[r] = cnt_at(u + 1);
-    }
-#pragma unroll
-    for (int r = 0; r < kB; r++) {
-      const int u = tid + r * kWT;
-      lv0[r] = nrel > 0 && u < nuniq && c0[r] != c1[r];
-      if (lv0[r]) {
-        int* d = dl + 3 * (c0[r] >> 16);
-        d[0] = (int)((unsigned)u | (m0[r] << 16));
-        d[1] = kx0[r];
-        d[2] = pa0[r];
-      }
+      if (!((relb >> r) & 1u)) continue;
+      const int c0 = base0[r] + x0[r], ri = c0 >> 16;
+      int* d = dl + 3 * ri;
+      d[0] = (int)((unsigned)(tid + r * kWT) | (m0[r] << 16));
+      d[1] = kx0[r];
+      d[2] = pa0[r];
+      dq[ri] = make_int2(c0 & 0xffff, pb0[r] - pa0[r]);
     }
   }
-  for (int u0 = tid + kB * kWT; u0 < nuniq && nrel > 0; u0 += kB * kWT) {
-    int kx[kB], po[kB];
-    unsigned msk[kB];
+  {
+    int run = tot1;  // packed count before the batch's slot r, wave 0
+    for (int ub = kBatch, bx = 0; ub < nuniq && nrel > 0; ub += kBatch, bx++) {
+      int kx[kB], po[kB], p1[kB];
+      unsigned msk[kB];
 #pragma unroll
-    for (int r = 0; r < kB; r++) {
-      const int uc = min(u0 + r * kWT, nuniq - 1);
-      kx[r] = A.plan.pkk[uc];
-      po[r] = A.plan.poff[uc];
-      msk[r] = A.plan.pmask[uc];
-    }
-    int c0[kB], c1[kB];
+      for (int r = 0; r < kB; r++) {
+        const int uc = min(ub + tid + r * kWT, nuniq - 1);
+        kx[r] = A.plan.pkk[uc];
+        po[r] = A.plan.poff[uc];
+        p1[r] = A.plan.poff[uc + 1];
+        msk[r] = A.plan.pmask[uc];
+      }
 #pragma unroll
-    for (int r = 0; r < kB; r++) {
-      const int uc = min(u0 + r * kWT, nuniq - 1);
-      c0[r] = cnt[uc];
-      c1[r] = cnt_at(uc + 1);
-    }
+      for (int r = 0; r < kB; r++) {
+        const int u = ub + tid + r * kWT;
+        int base = run;
 #pragma unroll
-    for (int r = 0; r < kB; r++) {
-      const int u = u0 + r * kWT;
-      if (u < nuniq && c0[r] != c1[r]) {
-        int* d = dl + 3 * (c0[r] >> 16);
-        d[0] = (int)((unsigned)u | (msk[r] << 16));
-        d[1] = kx[r];
-        d[2] = po[r];
+        for (int k = 0; k < kWT / 64; k++) {
+          const int w = wtx[bx * kTot + r * (kWT / 64) + k];
+          base += k < wid_s ? w : 0;
+          run += w;
+        }
+        if (u < nuniq && relevant(msk[r], u)) {
+          const int c0 = base + xs[u - kBatch], ri = c0 >> 16;
+          int* d = dl + 3 * ri;
+          d[0] = (int)((unsigned)u | (msk[r] << 16));
+          d[1] = kx[r];
+          d[2] = po[r];
+          dq[ri] = make_int2(c0 & 0xffff, p1[r] - po[r]);
+        }
       }
     }
   }
   __syncthreads();
-  // the record's patch values [0][1][1], [1][1][1], [2][1][1], [2][0][0]
-  // (ba_cuda.cu:282-285, :225) are loaded first: their round trip overlaps
-  // the record's LDS work
+  // Second batch.  The record's patch values [0][1][1], [1][1][1], [2][1][1],
+  // [2][0][0] (ba_cuda.cu:282-285, :225) go out first; the thread's first
+  // record keeps them in registers across the LDS-only barrier that ends the
+  // record stores, so the loads that need the record offsets join them in
+  // flight instead of waiting for them.
   const int c11 = P + 1;
-  for (int t = tid; t < nrel; t += kWT) {
+  float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f, v3 = 0.0f;
+  if (tid < nrel) {
+    const int* d = dl + 3 * tid;
+    const unsigned um = (unsigned)d[0];
+    const int kx = d[1];
+    const int2 qn = dq[tid];
+    const float* pk = A.patches + (size_t)kx * 3 * PP;
+    v0 = pk[c11], v1 = pk[PP + c11], v2 = pk[2 * PP + c11], v3 = pk[2 * PP];
+    record(tid, (int)(um & 0xffffu), kx, d[2], um >> 16, qn.x, qn.y);
+  }
+  for (int t = tid + kWT; t < nrel; t += kWT) {
     const int* d = dl + 3 * t;
     const unsigned um = (unsigned)d[0];
-    const int u = (int)(um & 0xffffu), kx = d[1];
+    const int kx = d[1];
+    const int2 qn = dq[t];
     const float* pk = A.patches + (size_t)kx * 3 * PP;
-    const float v0 = pk[c11], v1 = pk[PP + c11], v2 = pk[2 * PP + c11], v3 = pk[2 * PP];
-    record(u, kx, d[2], um >> 16, cnt[u], cnt_at(u + 1));
-    L.nxy[t] = make_float2((v0 - cx) / fx, (v1 - cy) / fy);
-    L.dep[t] = v2;
-    L.dbase[t] = v3;  // patch_retr_kernel reads [2][0][0] (:225)
+    const float w0 = pk[c11], w1 = pk[PP + c11], w2 = pk[2 * PP + c11], w3 = pk[2 * PP];
+    record(t, (int)(um & 0xffffu), kx, d[2], um >> 16, qn.x, qn.y);
+    L.nxy[t] = make_float2((w0 - cx) / fx, (w1 - cy) / fy);
+    L.dep[t] = w2;
+    L.dbase[t] = w3;  // patch_retr_kernel reads [2][0][0] (:225)
   }
   if (tid == 0) L.roff[nrel] = nrp;
-  __syncthreads();
+  lds_barrier();  // roff / rp / rpo complete; the patch values stay in flight
   mark(A, 42);
-  // pass B, second round trip: the edge ids of this thread's first kB
-  // relevant edges and the pose table, all issued before any is used
+  // the edge ids and slot pairs of this thread's first kB relevant edges (the
+  // positions of a patch are contiguous: poff[u] + t) and the fixed-pose rows
+  // of the pose table, all issued before any is used
   int ev0[kB];
+  unsigned ps0[kB];
 #pragma unroll
   for (int r = 0; r < kB; r++) {
     const int q = min(tid + r * kWT, max(nrp - 1, 0));
     const int ri = nrp > 0 ? L.rp[q] : 0;
     const int p = nrp > 0 ? rpo[ri] + (q - L.roff[ri]) : 0;
-    ev0[r] = A.plan.epos[min(max(p, 0), A.E - 1)];
+    const int pc = min(max(p, 0), A.E - 1);
+    ev0[r] = A.plan.epos[pc];
+    ps0[r] = A.plan.pslot[pc];
   }
-  // pose table: free poses t0.., then fixed ones from fmin
-  constexpr int kPr = kWSlots * 8 / kWT;
-  float pv[kPr];
+  float pvx[kPr];
 #pragma unroll
   for (int r = 0; r < kPr; r++) {
     const int k = tid + r * kWT, sl = k >> 3, c = k & 7;
-    const int gp = (sl < N) ? t0w + sl : fmin + (sl - N);
-    pv[r] = A.poses[7 * (size_t)min(max(gp, 0), A.num_poses - 1) + min(c, 6)];
+    const int gp = fmin != 0x7fffffff ? fmin + (sl - N) : 0;
+    pvx[r] = A.poses[7 * (size_t)min(max(gp, 0), A.num_poses - 1) + min(c, 6)];
   }
-#pragma unroll
-  for (int r = 0; r < kPr; r++) {
-    const int k = tid + r * kWT, sl = k >> 3, c = k & 7;
-    const int gp = (sl < N) ? t0w + sl : fmin + (sl - N);
-    const bool ok = c < 7 && gp >= 0 && gp < A.num_poses && (sl < N || fmin != 0x7fffffff);
-    L.pose[k] = ok ? pv[r] : ((c == 6) ? 1.0f : 0.0f);
+  if (tid < nrel) {
+    L.nxy[tid] = make_float2((v0 - cx) / fx, (v1 - cy) / fy);
+    L.dep[tid] = v2;
+    L.dbase[tid] = v3;  // patch_retr_kernel reads [2][0][0] (:225)
   }
   mark(A, 43);
-  // pass B, thread per relevant edge: slots, edge index, target/weight (the
-  // third round trip; further batches of kB edges per thread each need two)
+  // thread per relevant edge: target / weight by edge id (the third round
+  // trip; further batches of kB edges per thread each need two)
   for (int q0 = tid; q0 < nrp; q0 += kB * kWT) {
     int ev[kB];
+    unsigned ps[kB];
     if (q0 == tid) {
 #pragma unroll
-      for (int r = 0; r < kB; r++) ev[r] = ev0[r];
+      for (int r = 0; r < kB; r++) {
+        ev[r] = ev0[r];
+        ps[r] = ps0[r];
+      }
     } else {
 #pragma unroll
       for (int r = 0; r < kB; r++) {  // unconditional loads (see above)
         const int q = min(q0 + r * kWT, nrp - 1);
         const int ri = L.rp[q];
-        ev[r] = A.plan.epos[rpo[ri] + (q - L.roff[ri])];
+        const int p = rpo[ri] + (q - L.roff[ri]);
+        ev[r] = A.plan.epos[p];
+        ps[r] = A.plan.pslot[p];
       }
     }
-    int64_t gi[kB], gj[kB];
     float2 tg[kB], wt[kB];
 #pragma unroll
     for (int r = 0; r < kB; r++) {
       const int e = ev[r];
-      gi[r] = A.ii[e];
-      gj[r] = A.jj[e];
       tg[r] = reinterpret_cast<const float2*>(A.target)[e];
       wt[r] = reinterpret_cast<const float2*>(A.weight)[e];
     }
@@ -1703,11 +1791,18 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
     for (int r = 0; r < kB; r++) {
       const int q = q0 + r * kWT;
       if (q >= nrp) continue;
-      const unsigned si = wslot((int)gi[r], t0w, N, fmin), sj = wslot((int)gj[r], t0w, N, fmin);
-      L.ec[q] = (unsigned short)(si | (sj << 8));
+      L.ec[q] = (unsigned short)ps[r];
       L.eid[q] = ev[r];
       if (L.tw) L.tw[q] = make_float4(tg[r].x, tg[r].y, wt[r].x, wt[r].y);
     }
+  }
+  // pose table: free poses t0.., then fixed ones from fmin
+#pragma unroll
+  for (int r = 0; r < kPr; r++) {
+    const int k = tid + r * kWT, sl = k >> 3, c = k & 7;
+    const int gp = (sl < N) ? t0w + sl : (fmin != 0x7fffffff ? fmin + (sl - N) : -1);
+    const bool ok = c < 7 && gp >= 0 && gp < A.num_poses;
+    L.pose[k] = ok ? (sl < N ? pvf[r] : pvx[r]) : ((c == 6) ? 1.0f : 0.0f);
   }
   __syncthreads();
   mark(A, 1);
@@ -2088,7 +2183,7 @@ static size_t gran_count(int G) { return (size_t)2 * kGranPad * G; }
 // (Plan), which depend on E only, then the buffers of the iteration kernel for
 // a grid of G workgroups (callers that use the plan arrays alone pass G = 0).
 struct WScratch {
-  size_t epos, poff, pmask, pkk, meta;  // Plan
+  size_t epos, poff, pmask, pkk, meta, pslot;  // Plan
   size_t part, gran, ejg;               // WArgs
   size_t bytes;
 };
@@ -2105,6 +2200,7 @@ static WScratch window_scratch(int E, int G) {
   s.pmask = take(sizeof(unsigned) * (size_t)E);
   s.pkk = take(sizeof(int) * (size_t)E);
   s.meta = take(kMetaBytes);  // nuniq, fmin, status; [16, 28): int64 phase stamps
+  s.pslot = take(sizeof(unsigned short) * (size_t)E);  // behind the five pinned plan offsets
   s.part = take(sizeof(double) * 2 * kPartPad * (size_t)G);
   s.gran = take((size_t)16 * gran_count(G));
   s.ejg = take(sizeof(float) * 24 * (size_t)E);
@@ -2167,6 +2263,7 @@ static Plan plan_view(const BaProblem& p, const BaWindowWs& ws) {
   v.pmask = (unsigned*)(ws.scratch + s.pmask);
   v.pkk = (int*)(ws.scratch + s.pkk);
   v.meta = (int*)(ws.scratch + s.meta);
+  v.pslot = (unsigned short*)(ws.scratch + s.pslot);
   v.status = ws.status;
   v.sink = sink_for_device();
   v.t0d = p.t0d;

@@ -24,9 +24,9 @@ from dpvo_amd import altcorr, fastba, synthetic  # noqa: E402
 def ba_phases(m, iters=2):
     """Workgroup 0's phase table of the BA window kernel (as ba_window_phases.py)."""
     d = {"BA kernel (marks)": m[63] - m[0], "setup": m[1] - m[0],
-         "  plan entries + counts": m[40] - m[0], "  scan": m[41] - m[40],
-         "  records": m[42] - m[41], "  patch values, edge ids, poses": m[43] - m[42],
-         "  per-edge inputs": m[1] - m[43]}
+         "  first batch + wave prefixes": m[40] - m[0], "  prefix of the wave totals": m[41] - m[40],
+         "  records": m[42] - m[41], "  second batch issued, patch values": m[43] - m[42],
+         "  edge ids + slots, target / weight, poses": m[1] - m[43]}
     prev = 1
     for it in range(iters):
         mb = 2 + 8 * it
