@@ -62,6 +62,7 @@ def c_abi():
         _lib.dpvo_version.restype = ctypes.c_char_p
         _lib.dpvo_status_string.restype = ctypes.c_char_p
         _lib.dpvo_ba_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_ba_layer_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_update_packed_bytes.restype = ctypes.c_size_t
         _lib.dpvo_update_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_packed_bytes.restype = ctypes.c_size_t

@@ -1084,6 +1084,125 @@ torch::Tensor spd_solve_factored(torch::Tensor L, torch::Tensor B) {
   return X;
 }
 
+// The differentiable BA layer (dpvo/ba.py BA, 88-297): one Gauss-Newton step
+// and its adjoint (ba_layer.hip).  No host synchronisation in either call.
+struct LayerIn {
+  int E, M, p, N, dtype;
+};
+
+static LayerIn layer_inputs(torch::Tensor& poses, torch::Tensor& patches, torch::Tensor& intrinsics,
+                            torch::Tensor& ii, torch::Tensor& jj, torch::Tensor& kk) {
+  check_device(poses, "poses");
+  check_device(patches, "patches");
+  check_device(intrinsics, "intrinsics");
+  const auto dt = poses.scalar_type();
+  TORCH_CHECK(dt == torch::kFloat32 || dt == torch::kFloat64,
+              "cuda_ba.ba_layer: float32 or float64 tensors");
+  TORCH_CHECK(patches.scalar_type() == dt && intrinsics.scalar_type() == dt,
+              "cuda_ba.ba_layer: poses, patches and intrinsics must have one dtype");
+  TORCH_CHECK(poses.dim() >= 2 && poses.size(-1) == 7, "poses must be [.., N, 7]");
+  TORCH_CHECK(patches.dim() >= 4 && patches.size(-3) == 3 && patches.size(-1) == patches.size(-2),
+              "patches must be [.., M, 3, p, p]");
+  poses = poses.contiguous();
+  patches = patches.contiguous();
+  intrinsics = intrinsics.contiguous();
+  ii = idx64(ii, "ii");
+  jj = idx64(jj, "jj");
+  kk = idx64(kk, "kk");
+  LayerIn l;
+  l.E = ii.numel();
+  TORCH_CHECK(jj.numel() == l.E && kk.numel() == l.E, "ii, jj, kk must have equal length");
+  l.p = patches.size(-1);
+  l.N = poses.numel() / 7;
+  l.M = patches.numel() / (3 * (int64_t)l.p * l.p);
+  TORCH_CHECK(intrinsics.numel() == 4 * (int64_t)l.N, "intrinsics must be [.., N, 4]");
+  l.dtype = dtype_code(poses);
+  return l;
+}
+
+std::vector<torch::Tensor> ba_layer_forward(torch::Tensor poses, torch::Tensor patches,
+                                            torch::Tensor intrinsics, torch::Tensor targets,
+                                            torch::Tensor weights,
+                                            c10::optional<torch::Tensor> lmbda_dev, double lmbda,
+                                            torch::Tensor ii, torch::Tensor jj, torch::Tensor kk,
+                                            int64_t n, int64_t fixedp, bool structure_only,
+                                            std::vector<double> bounds, double ep,
+                                            bool with_backward) {
+  const LayerIn l = layer_inputs(poses, patches, intrinsics, ii, jj, kk);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  check_device(targets, "targets");
+  check_device(weights, "weights");
+  TORCH_CHECK(targets.scalar_type() == poses.scalar_type() &&
+                  weights.scalar_type() == poses.scalar_type(),
+              "cuda_ba.ba_layer_forward: targets / weights must have the dtype of poses");
+  TORCH_CHECK(targets.numel() == 2 * (int64_t)l.E && weights.numel() == 2 * (int64_t)l.E,
+              "targets / weights must be [.., E, 2]");
+  TORCH_CHECK(bounds.size() == 4, "bounds must hold 4 values");
+  TORCH_CHECK(fixedp >= 0 && n >= fixedp && n <= l.N, "cuda_ba.ba_layer_forward: need 0 <= fixedp <= "
+              "n <= N, got fixedp ", fixedp, ", n ", n, ", N ", l.N);
+  targets = targets.contiguous();
+  weights = weights.contiguous();
+  const void* lm = nullptr;
+  torch::Tensor lmt;
+  if (lmbda_dev && lmbda_dev->defined()) {
+    check_device(*lmbda_dev, "lmbda");
+    TORCH_CHECK(lmbda_dev->numel() == 1, "lmbda must be a float or a 1-element tensor");
+    lmt = lmbda_dev->to(poses.scalar_type()).contiguous();
+    lm = lmt.data_ptr();
+  }
+  const int nf = structure_only ? 0 : (int)(n - fixedp);
+  const bool none = l.E == 0;  // nothing launched: the outputs are the zero step
+  auto dX = none ? torch::zeros({nf, 6}, poses.options()) : torch::empty({nf, 6}, poses.options());
+  auto dZ = none ? torch::zeros({l.M}, poses.options()) : torch::empty({l.M}, poses.options());
+  const size_t wsb = dpvo_ba_layer_workspace_bytes(l.E, l.M, nf, with_backward ? 1 : 0);
+  auto ws = torch::empty({(int64_t)std::max<size_t>(wsb, 32)}, poses.options().dtype(torch::kUInt8));
+  if (l.E == 0) {
+    ws.zero_();
+    return {dX, dZ, ws};
+  }
+  check_status(dpvo_ba_layer_forward(poses.data_ptr(), patches.data_ptr(), intrinsics.data_ptr(),
+                                     targets.data_ptr(), weights.data_ptr(), lm, lmbda,
+                                     ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(),
+                                     kk.data_ptr<int64_t>(), l.E, l.M, l.p, l.N, (int)n, (int)fixedp,
+                                     structure_only ? 1 : 0, bounds.data(), ep, l.dtype,
+                                     dX.data_ptr(), dZ.data_ptr(), ws.data_ptr(), wsb,
+                                     with_backward ? 1 : 0, current_stream()),
+               "cuda_ba.ba_layer_forward");
+  return {dX, dZ, ws};
+}
+
+// -> [g_targets [E, 2], g_weights [E, 2], g_poses [N, 6], g_patches [M, 3]]
+std::vector<torch::Tensor> ba_layer_backward(torch::Tensor ws, torch::Tensor poses,
+                                             torch::Tensor patches, torch::Tensor intrinsics,
+                                             torch::Tensor ii, torch::Tensor jj, torch::Tensor kk,
+                                             torch::Tensor gX, torch::Tensor gZ, int64_t n,
+                                             int64_t fixedp, bool structure_only) {
+  const LayerIn l = layer_inputs(poses, patches, intrinsics, ii, jj, kk);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  check_device(ws, "ws");
+  check_device(gX, "gX");
+  check_device(gZ, "gZ");
+  const int nf = structure_only ? 0 : (int)(n - fixedp);
+  TORCH_CHECK(gX.scalar_type() == poses.scalar_type() && gZ.scalar_type() == poses.scalar_type(),
+              "cuda_ba.ba_layer_backward: gX / gZ must have the dtype of poses");
+  TORCH_CHECK(gX.numel() == 6 * (int64_t)nf && gZ.numel() == l.M,
+              "cuda_ba.ba_layer_backward: gX must be [n_free, 6] and gZ [M]");
+  gX = gX.contiguous();
+  gZ = gZ.contiguous();
+  const auto mk = [&](int64_t r, int64_t c) {  // every row is written by the kernels
+    return l.E == 0 ? torch::zeros({r, c}, poses.options()) : torch::empty({r, c}, poses.options());
+  };
+  auto gT = mk(l.E, 2), gW = mk(l.E, 2), gP = mk(l.N, 6), gK = mk(l.M, 3);
+  if (l.E == 0) return {gT, gW, gP, gK};
+  check_status(dpvo_ba_layer_backward(poses.data_ptr(), patches.data_ptr(), intrinsics.data_ptr(),
+                                      gX.data_ptr(), gZ.data_ptr(), l.E, l.M, l.p, l.N, (int)n,
+                                      (int)fixedp, structure_only ? 1 : 0, l.dtype, gT.data_ptr(),
+                                      gW.data_ptr(), gP.data_ptr(), gK.data_ptr(), ws.data_ptr(),
+                                      (size_t)ws.numel(), current_stream()),
+               "cuda_ba.ba_layer_backward");
+  return {gT, gW, gP, gK};
+}
+
 // PatchGraph.edges_loop (patchgraph.py:65-91) gated as dpvo.py:984-988
 void edges_loop(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics,
                 torch::Tensor ix, int64_t M, torch::Tensor st, int64_t n_cap,
@@ -1289,5 +1408,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "triangle read), B [..., n, k] -> [X, L (lower factor), info (first failed column, 0 = ok)]");
   m.def("spd_solve_factored", &spd_solve_factored,
         "X = (L L^T)^-1 B for a lower factor L from spd_solve (the backward's cholesky_solve)");
+  m.def("ba_layer_forward", &ba_layer_forward,
+        "one Gauss-Newton step of dpvo/ba.py BA: (poses, patches, intrinsics, targets, weights, "
+        "lmbda tensor or None, lmbda float, ii, jj, kk, n, fixedp, structure_only, bounds, ep, "
+        "with_backward) -> [dX [n_free, 6], dZ [M], workspace (int32 words: out-of-range edges, "
+        "factorisation info)]");
+  m.def("ba_layer_backward", &ba_layer_backward,
+        "adjoint of ba_layer_forward on its workspace: (ws, poses, patches, intrinsics, ii, jj, kk, "
+        "gX, gZ, n, fixedp, structure_only) -> [g_targets, g_weights, g_poses [N, 6], g_patches [M, 3]]");
   m.attr("native_library") = dpvo_version();
 }

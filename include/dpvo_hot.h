@@ -542,6 +542,42 @@ int dpvo_pg_remove_frame_dev(const int32_t* kf, int64_t* ii, int64_t* jj, int64_
 int dpvo_spd_solve(const void* H, const void* B, void* L, void* X, int32_t* info, int batch, int n,
                    int k, int factor, int dtype, void* stream);
 
+/* ------------------------------------------- differentiable BA layer (training) */
+
+/* One Gauss-Newton step of dpvo/ba.py BA (88-297), B = 1, and its adjoint
+   (ba_layer.hip).  poses [N, 7], patches [M, 3, p, p], intrinsics [N, 4],
+   targets / weights [E, 2] in `dtype` (DPVO_F32 / DPVO_F64; arithmetic and all
+   sums are fp64 in a fixed order), ii / jj / kk [E] int64.  n = number of
+   poses in the problem (fixedp <= n <= N), the free poses are [fixedp, n);
+   with structure_only the step has no pose part.  lmbda_dev (one element of
+   `dtype`, device) wins over the host value `lmbda` when not null.  bounds:
+   4 host doubles (xmin, ymin, xmax, ymax).  Gates: |r| < 250, Z > 0.2, the
+   bounds; an edge with ii / jj outside [0, n) or kk outside [0, M) is closed,
+   touches no memory and is counted in the first int32 of the workspace (the
+   second holds the factorisation's info: != 0 -> dX = 0).
+   Outputs: dX [n - fixedp, 6] (not written with structure_only), dZ [M].  The
+   workspace (dpvo_ba_layer_workspace_bytes(E, M, n_free, with_backward),
+   n_free = structure_only ? 0 : n - fixedp) carries the linearisation and the
+   factor to dpvo_ba_layer_backward, which must get the same buffer, sizes
+   and inputs:  gX [n_free, 6], gZ [M] -> g_targets / g_weights [E, 2],
+   g_poses [N, 6] (left tangent), g_patches [M, 3] (x, y, d of the centre).
+   E <= 0: DPVO_OK, no launch.  n < fixedp, n > N, p even or < 1, a dtype other
+   than F32 / F64, null pointers: DPVO_ERR_INVALID; 6 n_free beyond
+   dpvo_spd_solve's 8192: DPVO_ERR_UNSUPPORTED; short workspace:
+   DPVO_ERR_WORKSPACE (in that order).  8 launches forward, 7 backward. */
+size_t dpvo_ba_layer_workspace_bytes(int E, int M, int n_free, int with_backward);
+int dpvo_ba_layer_forward(const void* poses, const void* patches, const void* intrinsics,
+                          const void* targets, const void* weights, const void* lmbda_dev,
+                          double lmbda, const int64_t* ii, const int64_t* jj, const int64_t* kk,
+                          int E, int M, int p, int N, int n, int fixedp, int structure_only,
+                          const double* bounds, double ep, int dtype, void* dX, void* dZ, void* ws,
+                          size_t ws_bytes, int with_backward, void* stream);
+int dpvo_ba_layer_backward(const void* poses, const void* patches, const void* intrinsics,
+                           const void* gX, const void* gZ, int E, int M, int p, int N, int n,
+                           int fixedp, int structure_only, int dtype, void* g_targets,
+                           void* g_weights, void* g_poses, void* g_patches, void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- keyframe */
 
 /* DPVO.keyframe's decision (dpvo.py:586-599, 619-624) on the device.  st =
