@@ -37,7 +37,7 @@
 // Below the kernels: the C ABI of F-BA / F-REPROJ / F-NBR and the dispatch
 // between the three solvers (window, this one, large-graph: ba_paths.hpp).
 #include "common.hpp"
-#include "ba_device.hpp"  // bad::lin_edge: the one copy of the edge math
+#include "ba_device.hpp"  // bad::lin_edge (the one copy of the edge math), index helpers, rcp64
 #include "ba_paths.hpp"
 
 namespace dpvo {
@@ -124,14 +124,6 @@ static size_t iter_lds(int N) {
   return kCtlBytes + sizeof(double) * (42 * kIterWaves + n * (n + 1) + 36 + 6 * n);
 }
 
-__device__ __forceinline__ int tri_row(int t) {  // a with a(a+1)/2 <= t < (a+1)(a+2)/2
-  int r = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-  while (r * (r + 1) / 2 > t) r--;
-  while ((r + 1) * (r + 2) / 2 <= t) r++;
-  return r;
-}
-__device__ __forceinline__ int blk(int a, int b) { return a * (a + 1) / 2 + b; }  // a >= b
-
 __device__ __forceinline__ void trace(int64_t* tmark, int slot) {
   if (tmark && threadIdx.x == 0 && slot < kMarks) tmark[slot] = (int64_t)wall_clock64();
 }
@@ -139,6 +131,10 @@ __device__ __forceinline__ void trace(int64_t* tmark, int slot) {
 // ---------------------------------------------------------------------------
 // block-wide exclusive scan of data[0..n) in LDS (int), returns the total.
 // Callers barrier before (data complete); the scan ends with a barrier.
+// A run of ceil(n / T) elements per thread around block_excl_sum (scratch:
+// T/64 ints).  Not bad::fscan: its fixed 16 loads per thread cost
+// ba_setup_kernel 0.4 us at cfg2's two elements per thread
+// (profiles/device_helpers/kstats_summary.txt).
 // ---------------------------------------------------------------------------
 __device__ int block_exclusive_scan(int* data, int n, int* scratch) {
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -146,32 +142,13 @@ __device__ int block_exclusive_scan(int* data, int n, int* scratch) {
   const int lo = min(tid * per, n), hi = min(lo + per, n);
   int s = 0;
   for (int i = lo; i < hi; i++) s += data[i];
-  const int lane = tid & 63, wid = tid >> 6;
-  int v = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  if (lane == 63) scratch[wid] = v;
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int w = 0; w < nt / 64; w++) {
-      const int x = scratch[w];
-      scratch[w] = acc;
-      acc += x;
-    }
-    scratch[nt / 64] = acc;
-  }
-  __syncthreads();
-  int run = scratch[wid] + v - s;
+  int total;
+  int run = block_excl_sum(s, scratch, total);
   for (int i = lo; i < hi; i++) {
     const int x = data[i];
     data[i] = run;
     run += x;
   }
-  const int total = scratch[nt / 64];
   __syncthreads();
   return total;
 }
@@ -696,11 +673,6 @@ __device__ __forceinline__ void block_sum(const double* v, double* part, double*
 // every row block at each step folds the back substitution in, so the
 // critical path is one 6x6 inversion per pose.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double rcp_d(double x) {  // estimate + one Newton step
-  const double r = __builtin_amdgcn_rcp(x);
-  return __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
-}
-
 // one lane: in-place Gauss-Jordan inverse of an SPD 6x6 block (registers)
 __device__ __forceinline__ bool invert6(const double* M, int ld, double* Pinv) {
   double a[6][6];
@@ -713,7 +685,7 @@ __device__ __forceinline__ bool invert6(const double* M, int ld, double* Pinv) {
   for (int c = 0; c < 6; c++) {
     const double piv = a[c][c];
     ok = ok && (piv > 0.0);
-    const double r = rcp_d(piv);
+    const double r = bad::rcp64(piv);  // estimate + one Newton step
     a[c][c] = 1.0;
 #pragma unroll
     for (int j = 0; j < 6; j++) a[c][j] *= r;
@@ -881,8 +853,8 @@ __device__ void ba_solve_tail(const BaArgs& A, const BaWs& w, const double* S_in
         if (t < n * n) {
           const int r = t / n, c = t % n, ar = r / 6, ac = c / 6;
           // lower blocks hold (a, b), a >= b; the upper half is the transpose
-          v[j] = (ar >= ac) ? S_in[36 * blk(ar, ac) + 6 * (r % 6) + c % 6]
-                            : S_in[36 * blk(ac, ar) + 6 * (c % 6) + r % 6];
+          v[j] = (ar >= ac) ? S_in[36 * bad::lblk(ar, ac) + 6 * (r % 6) + c % 6]
+                            : S_in[36 * bad::lblk(ac, ar) + 6 * (c % 6) + r % 6];
         }
       }
 #pragma unroll
@@ -914,7 +886,9 @@ __global__ void __launch_bounds__(kIterThreads)
   int64_t* tr = trace_it ? w.tmark : nullptr;
   if (tid == 0) w.wgt[2 * blockIdx.x] = (int64_t)wall_clock64();
   {
-    const int d = blockIdx.x, a = tri_row(d), b = d - a * (a + 1) / 2;
+    const int d = blockIdx.x;
+    int a, b;
+    bad::tri_of(d, a, b);
     const double lam = (double)A.lmbda[0];
     const int nuniq = w.meta[0];
     double acc[42];  // 36 S entries + 6 y entries

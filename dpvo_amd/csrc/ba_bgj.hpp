@@ -12,6 +12,8 @@ namespace gba {
 constexpr int kGCap = 16;  // superblock poses (band half-width limit)
 constexpr int kMaxM = 6 * kGCap;
 
+// Not bad::rcp64 (ba_device.hpp, one Newton step): the large-graph pivots take
+// two, and the large-graph parity tests were set on these bits.
 __device__ __forceinline__ double rcp_f64(double p) {
   double r = __builtin_amdgcn_rcp(p);  // ~2^-26, then two Newton steps
   double e = fma(-p, r, 1.0);

@@ -334,7 +334,7 @@ __global__ void k_bscatter(int IB, Ws w) {
 // superblock size.
 __global__ void __launch_bounds__(1024) k_structure(int N, Ws w) {
   __shared__ int sflag[kMaxN];
-  __shared__ int wsum[32];
+  __shared__ int wsum[1024 / 64 + 1];
   __shared__ int sg;
   const int tid = threadIdx.x, nt = blockDim.x;
   Meta* meta = w.meta;
@@ -351,32 +351,13 @@ __global__ void __launch_bounds__(1024) k_structure(int N, Ws w) {
   }
   __syncthreads();
   // border flags -> bidx (exclusive scan of flags), cidx (of !flags); serial
-  // chunks per thread then a wave-level scan of the chunk sums.
+  // chunks per thread then a workgroup scan of the chunk sums.
   const int per = (N + nt - 1) / nt;
   const int lo = min(tid * per, N), hi = min(lo + per, N);
   int nb = 0;
   for (int a = lo; a < hi; a++) nb += sflag[a];
-  // block exclusive scan of nb (nt <= 1024 = 16 waves)
-  int x = nb;
-  const int lane = tid & 63, wid = tid >> 6;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(x, o, 64);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int q = 0; q < nt / 64; q++) {
-      const int v = wsum[q];
-      wsum[q] = acc;
-      acc += v;
-    }
-    wsum[31] = acc;
-  }
-  __syncthreads();
-  int bb = wsum[wid] + x - nb;  // border poses before lo
-  const int nB = wsum[31];
+  int nB;
+  int bb = block_excl_sum(nb, wsum, nB);  // border poses before lo
   for (int a = lo; a < hi; a++) {
     if (sflag[a]) {
       w.bidx[a] = bb;

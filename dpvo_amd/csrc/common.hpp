@@ -39,7 +39,6 @@ template <>
 __device__ __forceinline__ __half from_acc<__half>(float v) { return __float2half(v); }
 template <>
 __device__ __forceinline__ double from_acc<double>(float v) { return (double)v; }
-__device__ __forceinline__ double from_acc_d(double v) { return v; }
 
 // static_cast<int>(floor(v)) with out-of-range values pushed far outside
 // every map (the reference is undefined there; correlation_kernel.cu:156-157)
@@ -106,6 +105,28 @@ __device__ __forceinline__ int wave_min_i(int x) {
 __device__ __forceinline__ int wave_max_i(int x) {
   return __builtin_amdgcn_readlane(
       wave_scan_dpp(x, (int)0x80000000, [](int a, int b) { return a > b ? a : b; }), 63);
+}
+
+// Workgroup exclusive scan of one int per thread, in thread order: returns the
+// sum of v over the threads before this one, and in `total` the sum over all
+// of them (every thread gets both).  Called by every thread of a workgroup
+// of a multiple of 64 (at most 1024) threads.  One DPP scan per wave, the
+// wave totals through scr (LDS, blockDim.x / 64 ints; the callers keep the
+// blockDim.x / 64 + 1 of fscan), which every wave then scans for itself.
+// Two LDS barriers: one after the totals are written, one after they are
+// read -- so scr may be written again (the next call of a loop included) as
+// soon as the call returns.  No barrier before the first write: the caller
+// orders whatever it kept in scr before the call.
+__device__ __forceinline__ int block_excl_sum(int v, int* scr, int& total) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int incl = wave_incl_sum(v);
+  if (lane == 63) scr[wid] = incl;
+  lds_barrier();
+  const int t = lane < nw ? scr[lane] : 0;
+  const int tincl = wave_incl_sum(t);
+  lds_barrier();
+  total = __builtin_amdgcn_readlane(tincl, 63);
+  return __builtin_amdgcn_readlane(tincl - t, wave_uniform(wid)) + incl - v;
 }
 
 template <typename T>

@@ -430,13 +430,6 @@ __global__ void __launch_bounds__(kCorrWaves* kWave)
   }
 }
 
-template <typename T>
-__global__ void cast_from_f32_kernel(const float* __restrict__ in, T* __restrict__ out, size_t n) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x)
-    out[i] = from_acc<T>(in[i]);
-}
-
 // ---------------------------------------------------------------------------
 // A-PATCH / A-PATCH-BWD (correlation_kernel.cu:16-80): gather / scatter of a
 // (2R+2)^2 window per patch centre; one thread per output element, stores

@@ -79,11 +79,9 @@ __global__ void __launch_bounds__(kPgT) pg_plan_remove_kernel(
     lc_min = lc_on ? lc_min + n : -1;
   }
   __shared__ int wsum[kPgT / 64 + 1];
-  __shared__ int carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   const int num = counts[0], inac = counts[1];
-  if (tid == 0) carry[0] = carry[1] = 0;
-  __syncthreads();
+  int removed = 0;  // removed edges of the chunks before this one
   for (int base = 0; base < num; base += kPgT) {
     const int e = base + tid;
     int rm = 0;
@@ -97,38 +95,18 @@ __global__ void __launch_bounds__(kPgT) pg_plan_remove_kernel(
         if (rm && lc_min >= 0 && (a.jj[e] - a.ii[e]) > 30 && a.jj[e] > lc_min) rm = 0;
       }
     }
-    // workgroup inclusive scan of rm (removed) -> kept count = index - removed
-    int x = rm;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    if (tid == 0) {
-      int acc = 0;
-      for (int w = 0; w < kPgT / 64; w++) {
-        const int v = wsum[w];
-        wsum[w] = acc;
-        acc += v;
-      }
-      wsum[kPgT / 64] = acc;
-    }
-    __syncthreads();
-    const int rm_before = carry[1] + wsum[wid] + x - rm;  // removed edges before e
+    // workgroup exclusive scan of rm (removed) -> kept count = index - removed
+    int chunk_removed;
+    const int rm_before = removed + block_excl_sum(rm, wsum, chunk_removed);  // removed before e
     if (e < num) {
       const int kept_before = e - rm_before;
       // pos >= 0: new active slot; pos < 0: -(1 + inactive slot) or -1 - max (not stored)
       if (!rm) pos[e] = kept_before;
       else pos[e] = -(1 + ((store && inac + rm_before < max_edges) ? inac + rm_before : max_edges));
     }
-    __syncthreads();
-    if (tid == 0) carry[1] += wsum[kPgT / 64];
-    __syncthreads();
+    removed += chunk_removed;
   }
   if (tid == 0) {
-    const int removed = carry[1];
     counts[3] = num - removed;
     // the reference stores all or nothing (dpvo.py:539-553)
     const bool fits = inac + removed <= max_edges;

@@ -1,7 +1,8 @@
-// Standalone timing of the dense pose solve (ba_device.hpp chol32_solve) in
-// one 256-thread workgroup, with per-phase shader-clock stamps, against a host
-// fp64 Cholesky on a random SPD system shaped like a DPVO window.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I dpvo_amd/csrc \
+// Standalone timing of the retired fp32 dense pose solve (chol32_solve,
+// ba_chol32_experiment.hpp beside this file) in one 256-thread workgroup, with
+// per-phase shader-clock stamps, against a host fp64 Cholesky on a random SPD
+// system shaped like a DPVO window.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I dpvo_amd/csrc -I scripts/micro \
 //         scripts/micro/solve_bench.hip -o scripts/micro/solve_bench
 //   ./scripts/micro/solve_bench [N=11] [refine=1]
 #include <hip/hip_runtime.h>
@@ -12,7 +13,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ba_device.hpp"
+#include "ba_chol32_experiment.hpp"
 
 using namespace dpvo::bad;
 

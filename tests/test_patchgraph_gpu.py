@@ -118,6 +118,46 @@ def test_append_remove_sequence_matches_reference(gpu):
     _check(pg, ref)
 
 
+REMOVE_MASKS = {
+    "none": lambda n: np.zeros(n, bool),
+    "all": lambda n: np.ones(n, bool),
+    "every_other": lambda n: np.arange(n) % 2 == 0,
+    "last_only": lambda n: np.arange(n) == n - 1,
+}
+
+
+@pytest.mark.parametrize("mask", list(REMOVE_MASKS))
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_remove_at_scan_boundaries(gpu, n, mask):
+    """The remove kernel scans its flags in chunks of 1024 edges (one per
+    thread, 16 waves): edge counts at the wave and chunk boundaries, and two
+    chunks plus one edge for the count carried between chunks."""
+    from dpvo_amd.patchgraph import DevicePatchGraph
+
+    rng = np.random.default_rng(n)
+    M, DIM, max_edges = 16, 8, 2100
+    pg = DevicePatchGraph(max_edges=max_edges, DIM=DIM, device=gpu)
+    ref = RefPG(max_edges, DIM)
+    ix = np.repeat(np.arange(200), M).astype(np.int64)  # patch -> frame
+    kk = rng.integers(0, ix.size, n).astype(np.int64)
+    jj = rng.integers(0, 200, n).astype(np.int64)
+    pg.append_factors(torch.from_numpy(ix).to(gpu), torch.from_numpy(kk).to(gpu),
+                      torch.from_numpy(jj).to(gpu))
+    ref.append(ix, kk, jj)
+    w = rng.standard_normal((max_edges, 2)).astype(np.float32)
+    tg = rng.standard_normal((max_edges, 2)).astype(np.float32)
+    h = rng.standard_normal((max_edges, DIM)).astype(np.float32)
+    pg.weight[0].copy_(torch.from_numpy(w))
+    pg.target[0].copy_(torch.from_numpy(tg))
+    pg.net[0].copy_(torch.from_numpy(h))
+    ref.weight[:], ref.target[:], ref.net[:] = w, tg, h
+    m = np.zeros(max_edges, bool)
+    m[:n] = REMOVE_MASKS[mask](n)
+    pg.remove_factors(torch.from_numpy(m).to(gpu), True)
+    ref.remove(m, True)
+    _check(pg, ref)
+
+
 def test_window_rule_spares_loop_closure_edges(gpu):
     from dpvo_amd.patchgraph import DevicePatchGraph
 
