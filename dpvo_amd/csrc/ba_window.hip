@@ -67,15 +67,10 @@ constexpr long long kSpin = 2000000;    // 20 ms of the 100 MHz wall clock
 constexpr int kEpochWord = kWMaxG;      // flags[kWMaxG]: epoch of the last call
 constexpr int kFlagWords = kWMaxG + 8;
 constexpr int kRefine = 1;              // fp64 refinement steps of the solve
-// raw buffer resources (gfx950 dword 3) and the buffer builtins' cache-policy
-// bit for sc1 (agent-coherent: bypasses the CU's L1; stores write through L2)
-constexpr int kBufDword3 = 0x00020000;
-constexpr int kSc1 = 16;
+// (kBufDword3, kSc1, v4u and the write-through store: common.hpp)
 
 // status bits (shared with the other BA paths; see dpvo_hot.h)
 constexpr int kStChol = 1, kStClamp = 2, kStTimeout = 16, kStCap = 32;
-
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 // plan meta (ints): [0] nuniq, [1] fmin, [2] status, [3] shards that wrote
 // block-work partials; [16, 34) int64 phase stamps + 2 shader clocks; [kMetaWork + lblk(a, b)
@@ -1095,12 +1090,12 @@ __device__ void assemble(const WArgs& A, const WL& L, int nrel, int a, int b, do
           // bits; write-through (sc1) stores leave no dirty line in any XCD's
           // L2, so no stale copy of an earlier same-parity iteration can be
           // written back over a newer one (the L2s are not coherent)
-          const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-              A.ejg, 0, (int)(sizeof(float) * 24 * (size_t)A.E), kBufDword3);
+          const __amdgpu_buffer_rsrc_t rs =
+              wt_buffer(A.ejg, (int)(sizeof(float) * 24 * (size_t)A.E));
           const int o = (int)(sizeof(float) * 12 * ((size_t)par * A.E + L.eid[q]));
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, e0), rs, o, 0, kSc1);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, e1), rs, o + 16, 0, kSc1);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, e2), rs, o + 32, 0, kSc1);
+          wt_store16(rs, o, __builtin_bit_cast(v4u, e0));
+          wt_store16(rs, o + 16, __builtin_bit_cast(v4u, e1));
+          wt_store16(rs, o + 32, __builtin_bit_cast(v4u, e2));
         }
       }
       double* ps = pe + 14 * (size_t)(q - q0);
@@ -1303,9 +1298,8 @@ __device__ void reduce_acc(const double* acc, double* red, v4u* gout, unsigned l
   if (tid < NA) {
     const double* s = seg + 8 * tid;
     const double v = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(gout, 0, 16 * kGranPad, kBufDword3);
-    __builtin_amdgcn_raw_buffer_store_b128(granule(v, tag), rs, 16 * tid, 0, kSc1);  // needs no ordering
+    const __amdgpu_buffer_rsrc_t rs = wt_buffer(gout, 16 * kGranPad);
+    wt_store16(rs, 16 * tid, granule(v, tag));  // needs no ordering
   }
 }
 

@@ -61,6 +61,37 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// --- 16-B write-through stores ------------------------------------------------
+// raw buffer resources (gfx950 dword 3) and the buffer builtins' cache-policy
+// bit for sc1 (agent-coherent: bypasses the CU's L1; stores write through L2)
+constexpr int kBufDword3 = 0x00020000;
+constexpr int kSc1 = 16;
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+// A buffer of `bytes` bytes at `base` (wave-uniform).  Build it at the block or
+// slot that is written, not at the tensor: offsets are 32-bit and a store past
+// `bytes` is dropped.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_buffer(void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, kBufDword3);
+}
+// 16 B of one lane at byte offset `off` (a multiple of 16), write-through: the
+// line is not left dirty in the XCD's L2, so the bytes need no second trip at
+// the end-of-kernel release (and no stale copy can be written back later).
+// Only for 16 B per lane: a 4-B sc1 store costs about 6x, an 8-B one 2.7x per byte.
+__device__ __forceinline__ void wt_store16(__amdgpu_buffer_rsrc_t rs, int off, v4u v) {
+  __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, kSc1);
+}
+__device__ __forceinline__ void wt_store16(__amdgpu_buffer_rsrc_t rs, int off, float4 v) {
+  wt_store16(rs, off, __builtin_bit_cast(v4u, v));
+}
+// 16 B of one lane as a non-temporal store (the `nt` bit; not write-through: the
+// end-of-kernel release still publishes the line).  Which bulk writer takes
+// which flavour is decided by measurement: DESIGN.md, "What the bulk writers
+// leave behind".
+__device__ __forceinline__ void nt_store16(float* d, float4 v) {
+  __builtin_nontemporal_store(__builtin_bit_cast(v4u, v), reinterpret_cast<v4u*>(d));
+}
+
 // wave-uniform per-level parameter without a dynamic index into the kernel
 // argument struct (that would route every access through scratch / flat
 // loads, which count in vmcnt and force full drains in the tile loop)

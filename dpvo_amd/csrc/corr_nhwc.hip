@@ -457,23 +457,18 @@ __global__ void __launch_bounds__(kMaxL* kWave) __attribute__((amdgpu_waves_per_
     return q < half && (u == 0 ? pa < lim
                                : (paired && pa + half < lim && pa + half < x8 * per + per));
   };
-  {
-    const int sp = PAIRED ? 0 : w / L, lw = w - sp * L, q = j8 * npair + sp;
-    const int pA = x8 * per + q;
-    if (pair_ok(q, 0)) run_unit(pA, lw, outA);
-    if (pair_ok(q, 1)) run_unit(pA + half, L - 1 - lw, reinterpret_cast<float*>(stage));
-  }
-
-  // the edges' [nout][L] blocks from the waves' slices: whole lines, 16 B per
-  // lane when the block is a whole number of 16-B pieces
-  __syncthreads();
-  const int nl = nout * L, tid = threadIdx.x, nth = npair * L * kWave;
-#pragma unroll
-  for (int u2 = 0; u2 < (PAIRED ? 2 : 2 * kMaxL); u2++) {
-    const int sp = u2 >> 1, u = u2 & 1, q = j8 * npair + sp;
-    if (sp >= npair) break;
-    if (!pair_ok(q, u)) continue;
-    const int pos = x8 * per + q + (u ? half : 0);
+  // the [nout][L] block of the first (u = 0) or second edge of pair sp from the
+  // waves' slices, by nt threads of which this is thread t0: whole lines, 16 B
+  // per lane when the block is a whole number of 16-B pieces.  Those go out
+  // write-through: the whole grid is resident, so the 14.5 MB of a cfg2 call
+  // leave in the kernel's last microseconds, and as plain stores they would
+  // all be dirty in the L2s for the end-of-kernel release to write back
+  // (0.9 % of the step; non-temporal stores gained 0.6 %).  The scalar path
+  // stays plain: a 4-B write-through store costs about 6x a 16-B one per byte.
+  const int nl = nout * L;
+  const bool vec = L == kMaxL && (nl & 3) == 0;
+  auto store_block = [&](int sp, int u, int t0, int nt) __attribute__((always_inline)) {
+    const int pos = x8 * per + j8 * npair + sp + (u ? half : 0);
     const int edge = order ? wave_uniform(order[pos]) : pos;
     float* dst = out + (size_t)edge * nl;
     // level l of the pair's first edge is in wave sp L + l's own region, of
@@ -483,19 +478,40 @@ __global__ void __launch_bounds__(kMaxL* kWave) __attribute__((amdgpu_waves_per_
       const int wv = sp * L + (u == 0 ? l : L - 1 - l);
       return reinterpret_cast<const float*>(reinterpret_cast<const char*>(smem) + wv * wbytes + off);
     };
-    if (L == kMaxL && (nl & 3) == 0) {
+    if (vec) {
       const float* s0 = slice(0);
       const float* s1 = slice(1);
       const float* s2 = slice(2);
       const float* s3 = slice(3);
-      for (int o = tid; o < nout; o += nth)
-        *reinterpret_cast<float4*>(dst + 4 * o) = make_float4(s0[o], s1[o], s2[o], s3[o]);
+      const __amdgpu_buffer_rsrc_t rs = wt_buffer(dst, nl * (int)sizeof(float));
+      for (int o = t0; o < nout; o += nt)
+        wt_store16(rs, 16 * o, make_float4(s0[o], s1[o], s2[o], s3[o]));
     } else {
-      for (int e = tid; e < nl; e += nth) {
+      for (int e = t0; e < nl; e += nt) {
         const int o = e / L, l = e - o * L;
         dst[e] = slice(l)[o];
       }
     }
+  };
+  {
+    const int sp = PAIRED ? 0 : w / L, lw = w - sp * L, q = j8 * npair + sp;
+    const int pA = x8 * per + q;
+    if (pair_ok(q, 0)) run_unit(pA, lw, outA);
+    if (pair_ok(q, 1)) run_unit(pA + half, L - 1 - lw, reinterpret_cast<float*>(stage));
+  }
+
+  // the edges' blocks, by the whole workgroup (storing the first edge's block
+  // from the wave that completes it, while the others run their second units,
+  // was 0.3 % slower in the step than this: DESIGN.md, "What the bulk writers
+  // leave behind")
+  __syncthreads();
+  const int tid = threadIdx.x, nth = npair * L * kWave;
+#pragma unroll
+  for (int u2 = 0; u2 < (PAIRED ? 2 : 2 * kMaxL); u2++) {
+    const int sp = u2 >> 1, u = u2 & 1;
+    if (sp >= npair) break;
+    if (!pair_ok(j8 * npair + sp, u)) continue;
+    store_block(sp, u, tid, nth);
   }
 }
 
