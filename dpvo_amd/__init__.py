@@ -9,6 +9,8 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
   (net.py Patchifier, extractor.py BasicEncoder4)     -> dpvo_amd.Patchifier,
                      the feature encoders and gathers    dpvo_amd.BasicEncoder4
   (dpvo.py __call__ head, terminate / get_pose)      -> dpvo_amd.frontend
+  (dpvo.py DPVO, config.py, net.py VONet)            -> dpvo_amd.DPVO,
+                     the tracker class                   default_config, VONet
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -18,10 +20,18 @@ from ._native import EXT_NAMES, NATIVE_DIR, c_abi, load_extension  # noqa: F401
 __version__ = "0.1.0"
 
 __all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "frontend", "load_extension",
-           "c_abi", "BasicEncoder4", "Patchifier"]
+           "c_abi", "BasicEncoder4", "Patchifier", "tracker", "DPVO", "default_config", "VONet"]
 
 
-def __getattr__(name):  # the two classes, without importing torch.nn at package import
+def __getattr__(name):  # the classes, without importing torch.nn at package import
+    if name in ("DPVO", "default_config"):
+        from . import dpvo
+
+        return getattr(dpvo, name)
+    if name == "VONet":
+        from .net import VONet
+
+        return VONet
     if name == "BasicEncoder4":
         from .extractor import BasicEncoder4
 

@@ -1326,6 +1326,141 @@ std::vector<torch::Tensor> trajectory(torch::Tensor poses, torch::Tensor tstamps
   return {traj, root, info};
 }
 
+// ---- tracker.hip: the small kernels of the tracker's frame path ----------------
+static int ring_dtype(const torch::Tensor& t, const char* name) {
+  check_device(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kFloat16, name,
+              " must be float32 or float16");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous (written / read in place)");
+  return dtype_code(t);
+}
+
+// Patchifier's gathers and DPVO.__call__'s ring writes of frame n, one launch.
+void frame_sample(torch::Tensor fmap, torch::Tensor imap, torch::Tensor image,
+                  torch::Tensor coords, torch::Tensor gmap_ring, torch::Tensor imap_ring,
+                  torch::Tensor patches_out, torch::Tensor colors, int64_t res, int64_t n,
+                  c10::optional<torch::Tensor> n_dev) {
+  fmap = f32_contig(fmap, "fmap");
+  imap = f32_contig(imap, "imap");
+  image = f32_contig(image, "image");
+  coords = f32_contig(coords, "coords");
+  const int gd = ring_dtype(gmap_ring, "gmap ring");
+  TORCH_CHECK(ring_dtype(imap_ring, "imap ring") == gd, "the two rings must share one dtype");
+  check_device(patches_out, "patches_out");
+  check_device(colors, "colors");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(fmap.device());
+  TORCH_CHECK(fmap.dim() == 3 && imap.dim() == 3 && image.dim() == 3 && image.size(0) == 3,
+              "fmap [C, h, w], imap [DIM, h, w], image [3, H, W]");
+  const int64_t C = fmap.size(0), h = fmap.size(1), w = fmap.size(2), DIM = imap.size(0);
+  TORCH_CHECK(imap.size(1) == h && imap.size(2) == w, "fmap and imap differ in size");
+  TORCH_CHECK(coords.dim() == 2 && coords.size(1) == 2 && coords.size(0) > 0, "coords: [M, 2]");
+  const int64_t M = coords.size(0);
+  TORCH_CHECK(gmap_ring.dim() >= 3 && gmap_ring.size(-1) == gmap_ring.size(-2), "gmap ring: [.., C, P, P]");
+  const int64_t P = gmap_ring.size(-1);
+  TORCH_CHECK(gmap_ring.numel() % (M * C * P * P) == 0 && gmap_ring.numel() > 0,
+              "gmap ring: [pmem, M, C, P, P]");
+  const int64_t pmem = gmap_ring.numel() / (M * C * P * P);
+  TORCH_CHECK(imap_ring.numel() == pmem * M * DIM, "imap ring: [pmem, M, DIM]");
+  TORCH_CHECK(patches_out.scalar_type() == torch::kFloat32 && patches_out.is_contiguous() &&
+                  patches_out.numel() == M * 3 * P * P,
+              "patches_out: contiguous float32 [M, 3, P, P]");
+  TORCH_CHECK(colors.scalar_type() == torch::kUInt8 && colors.is_contiguous() &&
+                  colors.numel() % (3 * M) == 0 && colors.numel() > 0,
+              "colors: contiguous uint8 [N, M, 3]");
+  const int64_t N = colors.numel() / (3 * M);
+  TORCH_CHECK(N < (1LL << 31) && M < (1LL << 31) && pmem < (1LL << 31), "too large");
+  TORCH_CHECK(res > 0 && image.size(1) >= res * h && image.size(2) >= res * w,
+              "image must cover res x the feature map");
+  const int32_t* nd = (n_dev && n_dev->defined()) ? dev_scalar(*n_dev, "n") : nullptr;
+  TORCH_CHECK(nd || (n >= 0 && n < N), "frame_sample: n = ", n, " outside [0, ", N, ")");
+  check_status(dpvo_frame_sample(fmap.data_ptr<float>(), imap.data_ptr<float>(),
+                                 image.data_ptr<float>(), coords.data_ptr<float>(),
+                                 gmap_ring.data_ptr(), imap_ring.data_ptr(), gd,
+                                 patches_out.data_ptr<float>(), colors.data_ptr<uint8_t>(), (int)h,
+                                 (int)w, (int)image.size(1), (int)image.size(2), (int)C, (int)DIM,
+                                 (int)M, (int)P, (int)res, (int)pmem, (int)N, nd ? 0 : (int)n, nd,
+                                 current_stream()),
+               "cuda_ba.frame_sample");
+}
+
+// torch.quantile(delta.norm(dim=-1).float(), 0.5) -> fp32 device scalar
+torch::Tensor probe_median(torch::Tensor delta) {
+  check_device(delta, "delta");
+  TORCH_CHECK(delta.scalar_type() == torch::kFloat32 || delta.scalar_type() == torch::kFloat16,
+              "delta must be float32 or float16");
+  delta = delta.contiguous();
+  TORCH_CHECK(delta.numel() > 0 && delta.size(-1) == 2, "delta: [M, 2]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(delta.device());
+  const int64_t M = delta.numel() / 2;
+  TORCH_CHECK(M < (1LL << 31), "too large");
+  auto out = torch::empty({}, delta.options().dtype(torch::kFloat32));
+  check_status(dpvo_probe_median(delta.data_ptr(), dtype_code(delta), (int)M,
+                                 out.data_ptr<float>(), current_stream()),
+               "cuda_ba.probe_median");
+  return out;
+}
+
+// dpvo.py:805-810 into the patch graph's target / weight rows [0, E)
+void update_targets(torch::Tensor coords, torch::Tensor delta, torch::Tensor w,
+                    torch::Tensor target, torch::Tensor weight, int64_t E,
+                    c10::optional<torch::Tensor> E_dev) {
+  coords = f32_contig(coords, "coords");
+  check_device(delta, "delta");
+  check_device(w, "w");
+  check_device(target, "target");
+  check_device(weight, "weight");
+  TORCH_CHECK((delta.scalar_type() == torch::kFloat32 || delta.scalar_type() == torch::kFloat16) &&
+                  w.scalar_type() == delta.scalar_type(),
+              "delta / w must both be float32 or both float16");
+  delta = delta.contiguous();
+  w = w.contiguous();
+  TORCH_CHECK(target.scalar_type() == torch::kFloat32 && weight.scalar_type() == torch::kFloat32 &&
+                  target.is_contiguous() && weight.is_contiguous(),
+              "target / weight must be contiguous float32 (written in place)");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(coords.device());
+  TORCH_CHECK(coords.dim() >= 3 && coords.size(-1) == coords.size(-2), "coords: [.., E, 2, P, P]");
+  const int64_t P = coords.size(-1);
+  const int64_t cap = std::min({coords.numel() / (2 * P * P), delta.numel() / 2, w.numel() / 2,
+                                target.numel() / 2, weight.numel() / 2});
+  TORCH_CHECK(cap < (1LL << 30), "too large");
+  const int32_t* ed = (E_dev && E_dev->defined()) ? dev_scalar(*E_dev, "E") : nullptr;
+  TORCH_CHECK(ed || (E >= 0 && E <= cap), "update_targets: E = ", E, " outside [0, ", cap, "]");
+  check_status(dpvo_update_targets(coords.data_ptr<float>(), delta.data_ptr(), w.data_ptr(),
+                                   dtype_code(delta), target.data_ptr<float>(),
+                                   weight.data_ptr<float>(), (int)P, ed ? 0 : (int)E, ed, (int)cap,
+                                   current_stream()),
+               "cuda_ba.update_targets");
+}
+
+// dpvo.py:834-836, the centre pixel only, into points rows [0, m)
+void map_points(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics,
+                torch::Tensor ix, torch::Tensor points, int64_t m,
+                c10::optional<torch::Tensor> m_dev) {
+  poses = f32_contig(poses, "poses");
+  patches = f32_contig(patches, "patches");
+  intrinsics = f32_contig(intrinsics, "intrinsics");
+  ix = idx64(ix, "ix");
+  check_device(points, "points");
+  TORCH_CHECK(points.scalar_type() == torch::kFloat32 && points.is_contiguous() &&
+                  points.dim() == 2 && points.size(1) == 3,
+              "points: contiguous float32 [*, 3] (written in place)");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7 && poses.size(0) > 0, "poses: [N, 7]");
+  const int64_t N = poses.size(0);
+  TORCH_CHECK(intrinsics.numel() == 4 * N, "intrinsics: [N, 4]");
+  TORCH_CHECK(patches.dim() == 4 && patches.size(1) == 3 && patches.size(2) == patches.size(3),
+              "patches: [*, 3, P, P]");
+  const int64_t cap = std::min({patches.size(0), points.size(0), ix.numel()});
+  TORCH_CHECK(cap < (1LL << 31) && N < (1LL << 31), "too large");
+  const int32_t* md = (m_dev && m_dev->defined()) ? dev_scalar(*m_dev, "m") : nullptr;
+  TORCH_CHECK(md || (m >= 0 && m <= cap), "map_points: m = ", m, " outside [0, ", cap, "]");
+  check_status(dpvo_map_points(poses.data_ptr<float>(), patches.data_ptr<float>(),
+                               intrinsics.data_ptr<float>(), ix.data_ptr<int64_t>(),
+                               points.data_ptr<float>(), (int)N, (int)patches.size(-1),
+                               md ? 0 : (int)m, md, (int)cap, current_stream()),
+               "cuda_ba.map_points");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward", &ba_forward, "BA forward operator");
   m.def("neighbors", &ba_neighbors, "temporal neighboor indicies");
@@ -1397,6 +1532,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("poses"), py::arg("tstamps"), py::arg("n"), py::arg("n_dev"),
         py::arg("delta_log"), py::arg("delta_pairs"), py::arg("delta_count"), py::arg("counter"),
         py::arg("inverse"));
+  m.def("frame_sample", &frame_sample,
+        "Patchifier's gathers (net.py:388-399) and the ring / colour writes of DPVO.__call__ "
+        "(dpvo.py:937-938, 965-969) of frame n, one launch",
+        py::arg("fmap"), py::arg("imap"), py::arg("image"), py::arg("coords"),
+        py::arg("gmap_ring"), py::arg("imap_ring"), py::arg("patches_out"), py::arg("colors"),
+        py::arg("res"), py::arg("n"), py::arg("n_dev"));
+  m.def("probe_median", &probe_median,
+        "torch.quantile(delta.norm(dim=-1).float(), 0.5) (dpvo.py:584) -> fp32 device scalar",
+        py::arg("delta"));
+  m.def("update_targets", &update_targets,
+        "target = coords[..., P/2, P/2] + delta, weight = w for edges < E (dpvo.py:805-810)",
+        py::arg("coords"), py::arg("delta"), py::arg("w"), py::arg("target"), py::arg("weight"),
+        py::arg("E"), py::arg("E_dev"));
+  m.def("map_points", &map_points,
+        "centre-pixel point cloud of the first m patches (dpvo.py:834-836)", py::arg("poses"),
+        py::arg("patches"), py::arg("intrinsics"), py::arg("ix"), py::arg("points"), py::arg("m"),
+        py::arg("m_dev"));
   m.def("reproject_ordered_plan_insert", &ba_reproject_ordered_plan_insert,
         "reproject + edge order + BA plan + the new frame's pyramid insertion, one launch");
   m.def("reproject_ordered", &ba_reproject_ordered,

@@ -222,3 +222,32 @@ class Patchifier(nn.Module):
         if return_color:
             return fmap, gmap, imap, patches, index, clr
         return fmap, gmap, imap, patches, index
+
+
+class VONet(nn.Module):
+    """Container with ``dpvo.net.VONet``'s attribute names (net.py:426-434), so
+    a DPVO checkpoint's ``patchify.*`` / ``update.*`` keys load unchanged.
+    ``dtype`` is the packed weight type of both modules."""
+
+    def __init__(self, dtype=torch.float16):
+        super().__init__()
+        self.P = 3
+        self.patchify = Patchifier(self.P, dtype=dtype)
+        self.update = Update(p=self.P, dtype=dtype)
+        self.DIM = DIM
+        self.RES = 4
+
+    def load_checkpoint(self, path_or_state_dict):
+        """Load a DPVO checkpoint (a path for ``torch.load`` or a state dict):
+        a leading ``module.`` is stripped and keys containing ``update.lmbda``
+        are dropped, as DPVO.load_weights does; strict otherwise."""
+        sd = path_or_state_dict
+        if not isinstance(sd, dict):
+            sd = torch.load(sd, map_location="cpu")
+        new = {}
+        for k, v in sd.items():
+            if "update.lmbda" in k:
+                continue
+            new[k[len("module."):] if k.startswith("module.") else k] = v
+        self.load_state_dict(new, strict=True)
+        return self

@@ -676,6 +676,67 @@ int dpvo_trajectory(const float* poses, const int64_t* tstamps, int N, int n, co
                     float* traj, int64_t* root, int32_t* info, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ tracker */
+
+/* The four small kernels of the tracker's frame path (dpvo_amd/dpvo.py), one
+   launch each on `stream`, no host synchronisation, argument checks before
+   the launch.  Counts given as int32 device scalars (non-null *_dev) replace
+   the host value, as in dpvo_frame_init. */
+
+/* Patchifier.forward after the encoders (dpvo/net.py:388-399) plus the ring
+   writes of DPVO.__call__ (dpvo.py:937-938, 965-969), frame n = *n_dev or n.
+   For patch m with integer-valued centre (x, y) = coords[m] (clamped to
+   [P/2, w-1-P/2] x [P/2, h-1-P/2]) and ring row r = (n % pmem) M + m:
+     gmap_ring[r] [C, P, P]  = the P x P window of fmap [C, h, w] at the centre
+     imap_ring[r] [DIM]      = imap [DIM, h, w] at the centre
+                               (rings DPVO_F32 or DPVO_F16, round to nearest even)
+     patches_out[m] [3, P, P] = (x + dx, y + dy, 1)
+     colors[n, m, k] (uint8)  = (image[2-k] + 0.5) * 127.5 truncated, image
+                               [3, H, W] normalised fp32 read at pixel
+                               (res x + res/2, res y + res/2); two fp32
+                               roundings, no contraction (B, G, R order)
+   Exact copies: every output is bit-exact.  No other row is written.  One
+   wave per patch.  Null pointers, sizes <= 0, P even or larger than the map,
+   host n outside [0, N): DPVO_ERR_INVALID; another ring dtype or a map of 2^31
+   elements or more: DPVO_ERR_UNSUPPORTED; a device n outside [0, N) writes
+   nothing. */
+int dpvo_frame_sample(const float* fmap, const float* imap, const float* image,
+                      const float* coords, void* gmap_ring, void* imap_ring, int ring_dtype,
+                      float* patches_out, uint8_t* colors, int h, int w, int H, int W, int C,
+                      int DIM, int M, int P, int res, int pmem, int N, int n,
+                      const int32_t* n_dev, void* stream);
+
+/* torch.quantile(delta.norm(dim=-1).float(), 0.5) (dpvo.py:584): delta [M, 2]
+   (DPVO_F32, or DPVO_F16 widened first), out one fp32 device scalar.  Norms
+   sqrt(fma(y, y, x x)) in fp32 (torch's accumulation); rank select in LDS by one
+   workgroup; even M: b - (b - a) 0.5 over the two middle values (torch.lerp at
+   weight 0.5), odd M the middle value; NaN if any norm is NaN.  Null pointers,
+   M <= 0 or another dtype: DPVO_ERR_INVALID; M > 1024: DPVO_ERR_UNSUPPORTED. */
+int dpvo_probe_median(const void* delta, int dtype, int M, float* out, void* stream);
+
+/* dpvo.py:805-810 for edges e < E (E = *E_dev clamped to [0, cap], or the host
+   E <= cap; cap = rows of the buffers): target[e] = coords[e, :, P/2, P/2] +
+   (float)delta[e] (one fp32 add), weight[e] = (float)w[e].  coords [E, 2, P, P]
+   fp32; delta / w [E, 2] DPVO_F32 or DPVO_F16; target / weight [cap, 2] fp32.
+   Rows >= E are not written.  Host E == 0 (or cap == 0): DPVO_OK, no launch.
+   E < 0, E > cap, cap < 0, P even, another dtype, null pointers:
+   DPVO_ERR_INVALID. */
+int dpvo_update_targets(const float* coords, const void* delta, const void* w, int dtype,
+                        float* target, float* weight, int P, int E, const int32_t* E_dev,
+                        int cap, void* stream);
+
+/* The centre pixel of pops.point_cloud (dpvo.py:834-836) for patches k < m
+   (m = *m_dev clamped to [0, cap], or the host m <= cap; cap = rows of points
+   and of patches): points[k] = X.xyz / X.w with X = poses[ix[k]]^-1 *
+   ((x - cx) / fx, (y - cy) / fy, 1, d), (x, y, d) the centre of patch k and
+   the intrinsics of frame ix[k] (clamped to [0, N)).  fp64 arithmetic, the
+   quaternion normalised, rounded to fp32 on store; d == 0 divides.  Rows >= m
+   are not written.  Host m == 0 (or cap == 0): DPVO_OK, no launch.  m < 0,
+   m > cap, cap < 0, N <= 0, P even, null pointers: DPVO_ERR_INVALID. */
+int dpvo_map_points(const float* poses, const float* patches, const float* intrinsics,
+                    const int64_t* ix, float* points, int N, int P, int m, const int32_t* m_dev,
+                    int cap, void* stream);
+
 /* --------------------------------------------------------- update operator */
 
 /* DPVO's update operator, inference only (dpvo/net.py:175-339 `Update`, with
