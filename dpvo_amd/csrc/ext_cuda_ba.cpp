@@ -1461,7 +1461,118 @@ void map_points(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrin
                "cuda_ba.map_points");
 }
 
+// ---- match.hip / triangulate.hip: the front half of the long-term loop closure ---
+// -> [partner0 [N0], partner1 [N1], matches [min(N0, N1), 2] (int64), dist2, count (int32 [1])]
+std::vector<torch::Tensor> match_descriptors(torch::Tensor desc0, torch::Tensor desc1,
+                                             double ratio, double max_dist, int64_t n0,
+                                             c10::optional<torch::Tensor> n0_dev, int64_t n1,
+                                             c10::optional<torch::Tensor> n1_dev) {
+  check_device(desc0, "desc0");
+  check_device(desc1, "desc1");
+  TORCH_CHECK((desc0.scalar_type() == torch::kFloat32 || desc0.scalar_type() == torch::kFloat16) &&
+                  desc1.scalar_type() == desc0.scalar_type(),
+              "match_descriptors: desc0 / desc1 must both be float32 or both float16");
+  TORCH_CHECK(desc0.dim() == 2 && desc1.dim() == 2 && desc0.size(1) == desc1.size(1),
+              "match_descriptors: desc0 [N0, D], desc1 [N1, D]");
+  TORCH_CHECK(desc0.device() == desc1.device(), "match_descriptors: tensors on different devices");
+  const int64_t N0 = desc0.size(0), N1 = desc1.size(0), D = desc0.size(1);
+  TORCH_CHECK(N0 >= 1 && N1 >= 1 && N0 <= 4096 && N1 <= 4096,
+              "match_descriptors: 1 <= N0, N1 <= 4096, got ", N0, " and ", N1);
+  TORCH_CHECK(D >= 4 && D <= 256 && D % 4 == 0,
+              "match_descriptors: D must be a multiple of 4 in [4, 256], got ", D);
+  TORCH_CHECK(ratio >= 0.0 && max_dist >= 0.0, "match_descriptors: ratio and max_dist must be >= 0");
+  // rows are read four elements at a time: a view at an odd offset is copied
+  auto aligned = [](torch::Tensor t) {
+    t = t.contiguous();
+    const uintptr_t al = t.scalar_type() == torch::kFloat16 ? 7 : 15;
+    return ((uintptr_t)t.data_ptr() & al) ? t.clone() : t;
+  };
+  desc0 = aligned(desc0);
+  desc1 = aligned(desc1);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(desc0.device());
+  const int32_t* d0 = (n0_dev && n0_dev->defined()) ? dev_scalar(*n0_dev, "n0") : nullptr;
+  const int32_t* d1 = (n1_dev && n1_dev->defined()) ? dev_scalar(*n1_dev, "n1") : nullptr;
+  // a host limit is clamped to the rows present, as a device one is
+  n0 = std::min(std::max(n0, (int64_t)0), N0);
+  n1 = std::min(std::max(n1, (int64_t)0), N1);
+  const auto i64 = desc0.options().dtype(torch::kInt64);
+  const int64_t K = std::min(N0, N1);
+  auto partner0 = torch::empty({N0}, i64), partner1 = torch::empty({N1}, i64);
+  auto matches = torch::empty({K, 2}, i64);
+  auto dist2 = torch::empty({K}, desc0.options().dtype(torch::kFloat32));
+  auto count = torch::empty({1}, desc0.options().dtype(torch::kInt32));
+  const size_t wsb = dpvo_match_workspace_bytes((int)N0, (int)N1);
+  auto ws = torch::empty({(int64_t)wsb}, desc0.options().dtype(torch::kUInt8));
+  const float r2 = (float)(ratio * ratio), md2 = (float)(max_dist * max_dist);
+  check_status(dpvo_match_descriptors(desc0.data_ptr(), desc1.data_ptr(), dtype_code(desc0),
+                                      (int)N0, (int)N1, (int)D, d0 ? 0 : (int)n0, d0,
+                                      d1 ? 0 : (int)n1, d1, r2, md2, partner0.data_ptr<int64_t>(),
+                                      partner1.data_ptr<int64_t>(), matches.data_ptr<int64_t>(),
+                                      dist2.data_ptr<float>(), count.data_ptr<int32_t>(),
+                                      ws.data_ptr(), wsb, current_stream()),
+               "cuda_ba.match_descriptors");
+  return {partner0, partner1, matches, dist2, count};
+}
+
+// -> [points [N1, 3], disp [N1], keep [N1] (bool), sel [N1] (int64), count (int32 [1])]
+std::vector<torch::Tensor> triangulate_tracks(torch::Tensor poses, torch::Tensor intrinsics,
+                                              torch::Tensor disps, torch::Tensor kps0,
+                                              torch::Tensor kps1, torch::Tensor kps2,
+                                              torch::Tensor m10, torch::Tensor m12,
+                                              double max_depth, double max_residual,
+                                              int64_t iterations, double lmbda) {
+  poses = f32_contig(poses, "poses");
+  intrinsics = f32_contig(intrinsics, "intrinsics");
+  kps0 = f32_contig(kps0, "kps0");
+  kps1 = f32_contig(kps1, "kps1");
+  kps2 = f32_contig(kps2, "kps2");
+  m10 = idx64(m10, "m10");
+  m12 = idx64(m12, "m12");
+  check_device(disps, "disps");
+  TORCH_CHECK(disps.scalar_type() == torch::kFloat32 && disps.dim() == 1 && disps.numel() >= 1,
+              "triangulate_tracks: disps must be float32 [M]");
+  if (disps.stride(0) < 1) disps = disps.contiguous();
+  TORCH_CHECK(poses.numel() == 21 && intrinsics.numel() == 12,
+              "triangulate_tracks: poses [3, 7] and intrinsics [3, 4] of frames i-1, i, i+1");
+  for (const auto* k : {&kps0, &kps1, &kps2})
+    TORCH_CHECK(k->dim() == 2 && k->size(1) == 2 && k->size(0) >= 1,
+                "triangulate_tracks: keypoints must be [N, 2] with N >= 1");
+  const int64_t M = disps.numel(), N0 = kps0.size(0), N1 = kps1.size(0), N2 = kps2.size(0);
+  TORCH_CHECK(m10.numel() == N1 && m12.numel() == N1, "triangulate_tracks: m10 / m12 must be [N1]");
+  TORCH_CHECK(M <= 1024, "triangulate_tracks: M <= 1024, got ", M);
+  TORCH_CHECK(N1 <= 4096 && N0 < (1LL << 31) && N2 < (1LL << 31) && disps.stride(0) < (1LL << 31),
+              "triangulate_tracks: N1 <= 4096, got ", N1);
+  TORCH_CHECK(iterations >= 0 && lmbda >= 0.0, "triangulate_tracks: iterations, lmbda >= 0");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  auto points = torch::empty({N1, 3}, poses.options());
+  auto disp = torch::empty({N1}, poses.options());
+  auto keep = torch::empty({N1}, poses.options().dtype(torch::kBool));
+  auto sel = torch::empty({N1}, poses.options().dtype(torch::kInt64));
+  auto count = torch::empty({1}, poses.options().dtype(torch::kInt32));
+  check_status(dpvo_triangulate_tracks(
+                   poses.data_ptr<float>(), intrinsics.data_ptr<float>(), disps.data_ptr<float>(),
+                   (int)disps.stride(0), (int)M, kps0.data_ptr<float>(), (int)N0,
+                   kps1.data_ptr<float>(), (int)N1, kps2.data_ptr<float>(), (int)N2,
+                   m10.data_ptr<int64_t>(), m12.data_ptr<int64_t>(), (float)max_depth,
+                   (float)max_residual, (int)iterations, (float)lmbda, points.data_ptr<float>(),
+                   disp.data_ptr<float>(), reinterpret_cast<uint8_t*>(keep.data_ptr<bool>()),
+                   sel.data_ptr<int64_t>(), count.data_ptr<int32_t>(), current_stream()),
+               "cuda_ba.triangulate_tracks");
+  return {points, disp, keep, sel, count};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("match_descriptors", &match_descriptors,
+        "mutual nearest neighbours of two descriptor sets with a ratio test, two launches -> "
+        "[partner0, partner1, matches, dist2, count]",
+        py::arg("desc0"), py::arg("desc1"), py::arg("ratio"), py::arg("max_dist"), py::arg("n0"),
+        py::arg("n0_dev"), py::arg("n1"), py::arg("n1_dev"));
+  m.def("triangulate_tracks", &triangulate_tracks,
+        "3-D keypoints of frame i from its tracks over i-1, i, i+1 (long_term.py:90-136), one "
+        "launch -> [points, disp, keep, sel, count]",
+        py::arg("poses"), py::arg("intrinsics"), py::arg("disps"), py::arg("kps0"),
+        py::arg("kps1"), py::arg("kps2"), py::arg("m10"), py::arg("m12"), py::arg("max_depth"),
+        py::arg("max_residual"), py::arg("iterations"), py::arg("lmbda"));
   m.def("forward", &ba_forward, "BA forward operator");
   m.def("neighbors", &ba_neighbors, "temporal neighboor indicies");
   m.def("reproject", &ba_reproject, "temporal neighboor indicies");

@@ -18,6 +18,11 @@ the motion probe's decision.
 or any object with `.patchify`, `.update`, `.DIM`, `.RES` and `.P`: with a
 `VONet` the tracker runs the two encoders and frame_sample itself, with any
 other object it calls `network.patchify(...)` as the reference does.
+
+With cfg.CLASSIC_LOOP_CLOSURE the tracker drives a `long_term.LongTermLoopClosure`
+given as `loop_closure=` (the object, or a callable (cfg, slam) -> one) at the
+reference's four sites: the raw image of every frame, the index of a dropped
+keyframe, an attempt after every tracked frame, and terminate.
 """
 from __future__ import annotations
 
@@ -49,8 +54,8 @@ class DPVO:
     LEVELS = (1, 4)
 
     def __init__(self, cfg, network, ht=480, wd=640, device="cuda", ba_iterations=1,
-                 generator=None):
-        if cfg.CLASSIC_LOOP_CLOSURE:
+                 generator=None, loop_closure=None):
+        if cfg.CLASSIC_LOOP_CLOSURE and loop_closure is None:
             raise NotImplementedError(
                 "CLASSIC_LOOP_CLOSURE: the retrieval backend is not part of the tracker; drive "
                 "loop_closure.close_loop / loop_closure.apply_result from the caller")
@@ -121,6 +126,12 @@ class DPVO:
         self.last_root = None
         self.updates = 0
         self.global_ba_runs = 0
+        # the long-term loop closure (dpvo.py:179-185): a long_term.LongTermLoopClosure, or a
+        # callable (cfg, slam) -> one; never touched unless CLASSIC_LOOP_CLOSURE is set
+        self.long_term_lc = None
+        if cfg.CLASSIC_LOOP_CLOSURE:
+            self.long_term_lc = (loop_closure if hasattr(loop_closure, "attempt_loop_closure")
+                                 else loop_closure(cfg, self))
 
     # -- network ---------------------------------------------------------------
     def _load_network(self, network):
@@ -330,6 +341,10 @@ class DPVO:
             rings.append(mem)
         frames += [self.imap_.view(pmem, -1), self.gmap_.view(pmem, -1)]
         rings += [pmem, pmem]
+        if self.long_term_lc is not None:  # the frame cache's slot table moves with the frames
+            frames.append(self.long_term_lc.frame_table())
+            rings.append(0)
+        n_before = self.n
         self._set_counts()
         self.pg.keyframe(self._st, self.poses_, self.patches_, self.intrinsics_, self.M,
                          frames=frames, rings=rings, tstamps=self.tstamps_,
@@ -340,6 +355,8 @@ class DPVO:
                                      loop_closure=bool(cfg.LOOP_CLOSURE),
                                      optimization_window=int(cfg.OPTIMIZATION_WINDOW))
         self.n, self.m = (int(v) for v in self._st.tolist())
+        if self.long_term_lc is not None and self.n < n_before:  # dpvo.py:675-676
+            self.long_term_lc.keyframe(n_before - int(cfg.KEYFRAME_INDEX))
 
     # -- dpvo.py:905-1030 --------------------------------------------------------
     @torch.no_grad()
@@ -351,6 +368,8 @@ class DPVO:
         if image.dim() != 3 or image.shape[0] != 3 or tuple(image.shape[1:]) != (self.ht, self.wd):
             raise ValueError(f"DPVO: image must be [3, {self.ht}, {self.wd}], got "
                              f"{tuple(image.shape)}")
+        if self.long_term_lc is not None:  # dpvo.py:908-909: the raw image
+            self.long_term_lc(image, self.n)
         image = image.to(self.dev)
         image = (2 * (image / 255.0) - 0.5).float().contiguous()
         intrinsics = torch.as_tensor(intrinsics, dtype=torch.float32).to(self.dev)
@@ -397,6 +416,8 @@ class DPVO:
         elif self.is_initialized:
             self.update()
             self.keyframe()
+        if self.long_term_lc is not None:  # dpvo.py:1027-1028
+            self.long_term_lc.attempt_loop_closure(self.n)
 
     # -- dpvo.py:385-417 ---------------------------------------------------------
     def _trajectory(self, inverse):
@@ -416,6 +437,8 @@ class DPVO:
     def terminate(self):
         """Final updates and the trajectory -> (poses [counter, 7] float32,
         inverted as the reference returns them; tstamps float64)."""
+        if self.long_term_lc is not None:  # dpvo.py:394-395
+            self.long_term_lc.terminate(self.n)
         if self.cfg.LOOP_CLOSURE:
             self._set_counts()
             self._loop_edges(gated=False)

@@ -228,8 +228,10 @@ def close_loop(poses_, n, loop_ii, loop_jj, i, j, i_pts, j_pts, min_inliers=30, 
     if status != 0 or num_inliers < min_inliers:
         return None
     poses_ = poses_.view(-1, 7)
-    Gij = SE3(poses_[loop_jj]) * SE3(poses_[loop_ii]).inv()
-    loop_poses = torch.cat([SE3_to_Sim3(Gij).data, est.sim3[None].to(poses_.dtype)], dim=0)
+    loop_poses = est.sim3[None].to(poses_.dtype)
+    if loop_ii.numel() > 0:  # the first loop has no earlier ones to join
+        Gij = SE3(poses_[loop_jj]) * SE3(poses_[loop_ii]).inv()
+        loop_poses = torch.cat([SE3_to_Sim3(Gij).data, loop_poses], dim=0)
     new = torch.tensor([i, j], device=loop_ii.device, dtype=loop_ii.dtype)
     loop_ii = torch.cat([loop_ii, new[:1]])
     loop_jj = torch.cat([loop_jj, new[1:]])

@@ -737,6 +737,66 @@ int dpvo_map_points(const float* poses, const float* patches, const float* intri
                     const int64_t* ix, float* points, int N, int P, int m, const int32_t* m_dev,
                     int cap, void* stream);
 
+/* ------------------------------------------------- long-term loop closure */
+
+/* Mutual nearest neighbours of two descriptor sets with a ratio test (the
+   matcher between the detector and dpvo_ransac_umeyama; it stands where the
+   reference runs LightGlue, long_term.py:82-88, 228-229).  desc0 [N0, D],
+   desc1 [N1, D], contiguous, DPVO_F32 or DPVO_F16 (widened exactly), rows
+   aligned to four elements; 1 <= N0, N1 <= 4096, D % 4 == 0, 4 <= D <= 256.
+   Rows i < n0 / j < n1 are valid (n = *n_dev where n_dev is not null, else the
+   host n; clamped to [0, N]); the others are never read.  All in fp32:
+     sim[i, j] = sum_d a[i, d] b[j, d]        an fma chain, d ascending
+     d2[i, j]  = max((|a_i|^2 + |b_j|^2) - 2 sim[i, j], 0)
+   Every row takes its best column (smaller d2, then the lower index) and the
+   second-best d2 (+inf with one valid column), every column likewise; (i, j)
+   is a match when each is the other's best, d2 <= ratio2 * second on both
+   sides (one fp32 product) and d2 <= max_dist2.
+     partner0 [N0] / partner1 [N1] (int64)  the matched column / row, or -1
+     matches [min(N0, N1), 2] (int64)       the pairs by ascending i, then -1
+     dist2 [min(N0, N1)]                    d2 of each pair, then -1
+     count                                  the number of pairs
+   Two launches (64 x 64 tiles on v_mfma_f32_32x32x2_f32 reduced to top-2
+   triples, then one workgroup that merges, tests and compacts), no host sync,
+   no atomics: two runs are bit-equal.  Null pointers, N < 1, D < 4, D % 4 != 0,
+   another dtype, a host n outside [0, N], a negative or NaN ratio2 /
+   max_dist2, misaligned rows: DPVO_ERR_INVALID; N > 4096 or D > 256:
+   DPVO_ERR_UNSUPPORTED; short workspace: DPVO_ERR_WORKSPACE (in that order).
+   dpvo_match_workspace_bytes is 0 outside 1 <= N <= 4096. */
+size_t dpvo_match_workspace_bytes(int N0, int N1);
+int dpvo_match_descriptors(const void* desc0, const void* desc1, int dtype, int N0, int N1, int D,
+                           int n0, const int32_t* n0_dev, int n1, const int32_t* n1_dev,
+                           float ratio2, float max_dist2, int64_t* partner0, int64_t* partner1,
+                           int64_t* matches, float* dist2, int32_t* count, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* The 3-D keypoints of frame i from its tracks over the frames i-1, i, i+1
+   (long_term.py:90-136 joined with the depth filter of :213-217).  poses [3, 7]
+   and intrinsics [3, 4] (at image resolution) of the three frames; disps: M
+   inverse depths `disp_stride` floats apart (the centre pixels of frame i's
+   patches); kps0 [N0, 2], kps1 [N1, 2], kps2 [N2, 2] in image pixels; m10 /
+   m12 [N1]: the partner of keypoint n of frame i in kps0 / kps2, or -1.  A
+   keypoint with both partners in range is a track: its inverse depth starts at
+   the lower median of disps (torch.median) and takes `iterations` steps
+   dZ = u / (C + lmbda) of the structure-only BA over its two observations,
+   weight 1, linearised, gated and clamped as dpvo_ba_forward does (fp32 edge
+   math, fp64 sums).  Then
+     points [N1, 3]  ((u - cx) / fx, (v - cy) / fy, 1) / d, intrinsics of frame i
+     disp [N1]       d (0 where the keypoint is no track, as are its points)
+     keep [N1]       track, both reprojection residuals < max_residual and
+                     points.z < max_depth
+     sel [N1]        the kept indices in ascending order, then -1 (int64)
+     count           their number
+   One launch of one workgroup, no host sync.  Null pointers, M / N0 / N1 / N2 /
+   disp_stride < 1, iterations < 0, a negative or NaN lmbda: DPVO_ERR_INVALID;
+   M > 1024 or N1 > 4096: DPVO_ERR_UNSUPPORTED. */
+int dpvo_triangulate_tracks(const float* poses, const float* intrinsics, const float* disps,
+                            int disp_stride, int M, const float* kps0, int N0, const float* kps1,
+                            int N1, const float* kps2, int N2, const int64_t* m10,
+                            const int64_t* m12, float max_depth, float max_residual,
+                            int iterations, float lmbda, float* points, float* disp,
+                            uint8_t* keep, int64_t* sel, int32_t* count, void* stream);
+
 /* --------------------------------------------------------- update operator */
 
 /* DPVO's update operator, inference only (dpvo/net.py:175-339 `Update`, with
