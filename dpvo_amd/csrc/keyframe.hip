@@ -476,6 +476,9 @@ DPVO_EXPORT int dpvo_kf_motion(const int64_t* ii, const int64_t* jj, const int64
   if (!ii || !jj || !kk || !counts || !poses || !patches || !intrinsics || !st || !kf || !mag ||
       P <= 0 || keyframe_index < 1)
     return DPVO_ERR_INVALID;
+  // a drop moves keyframe_index - 1 frames and kf_shift_frames_kernel holds at
+  // most kMaxMoved of them: refuse the decision that would predicate such a drop
+  if (keyframe_index - 1 > kMaxMoved) return DPVO_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(kf_motion_kernel, dim3(1), dim3(kKfT), 0, as_stream(stream), ii, jj, kk,
                      (const int*)counts, poses, patches, intrinsics, P, (const int*)st,
                      keyframe_index, keyframe_thresh, (int*)kf, mag);
@@ -489,8 +492,9 @@ DPVO_EXPORT int dpvo_kf_shift(const int32_t* kf, int M, int32_t* st, int64_t* ii
                               const int64_t* tstamps, float* delta_log, int64_t* delta_tstamps,
                               int32_t* delta_count, int delta_cap, void* stream) {
   if (!kf || !st || !ii || !jj || !kk || !counts || M <= 0 || max_edges <= 0 || narrays < 0 ||
-      narrays > kMaxShift || (narrays && (!frame_arrays || !bytes_per_frame || !ring)))
+      (narrays && (!frame_arrays || !bytes_per_frame || !ring)))
     return DPVO_ERR_INVALID;
+  if (narrays > kMaxShift) return DPVO_ERR_UNSUPPORTED;  // ShiftArrays is a launch argument
   const bool log = delta_log || delta_tstamps || delta_count;
   if (log && (!delta_log || !delta_tstamps || !delta_count || !poses || !tstamps || delta_cap <= 0))
     return DPVO_ERR_INVALID;
@@ -530,6 +534,11 @@ DPVO_EXPORT int dpvo_edges_loop(const float* poses, const float* patches, const 
   if (!poses || !patches || !intrinsics || !ix || !st || !work || !out_kk || !out_jj || !out_n ||
       P < 2 || M <= 0 || n_cap < 0 || removal_window < 0 || max_edge_age < 0 || nms < 0 ||
       max_num_edges < 0)
+    return DPVO_ERR_INVALID;
+  // target frames j in [n - global_opt_freq, n - keyframe_index) for every
+  // n > removal_window: j >= 0 needs global_opt_freq <= removal_window + 1,
+  // j < n needs keyframe_index >= 0 (el_groups_kernel reads poses + 7 j)
+  if (keyframe_index < 0 || (long long)global_opt_freq > (long long)removal_window + 1)
     return DPVO_ERR_INVALID;
   LoopCfg c;
   c.P = P;

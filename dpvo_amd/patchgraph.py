@@ -134,7 +134,32 @@ class DevicePatchGraph:
         poses / patches / intrinsics / tstamps are the per-frame buffers
         (patches [N*M,3,P,P]); they are shifted too.  delta = (log [cap,7],
         tstamps [cap,2] (t1, t0), count int32[1]) records pg.delta.
-        Returns (kf, mag) device tensors."""
+        Returns (kf, mag) device tensors.
+
+        Limits, checked before anything is launched (the graph and st are
+        untouched when they raise): a drop moves keyframe_index - 1 frames and
+        the kernel holds at most 16, so keyframe_index <= 17; every ring size
+        is 0 or > keyframe_index - 1 (the kernel reads all moved rows of a
+        word before it writes them; the reference copies frame by frame and,
+        in a ring no larger than the number of moved frames, re-reads rows it
+        has already overwritten)."""
+        if len(frames) != len(rings):
+            raise ValueError("one ring size per frame array")
+        if 3 + (tstamps is not None) + len(frames) > 12:
+            raise ValueError("at most 12 per-frame arrays move in one launch (poses, patches, "
+                             "intrinsics and tstamps included)")
+        if delta is not None and tstamps is None:
+            raise ValueError("the delta log needs tstamps")
+        nm = int(keyframe_index) - 1
+        if nm > 16:
+            raise ValueError(f"keyframe_index={int(keyframe_index)}: a frame drop moves "
+                             f"keyframe_index - 1 = {nm} frames, the device shift holds at most 16")
+        for r in rings:
+            if 0 < int(r) <= nm:
+                raise ValueError(f"ring size {int(r)} <= keyframe_index - 1 = {nm}: a frame drop "
+                                 "moves that many frames and the rows would wrap onto each other "
+                                 "(the frame-by-frame copy of the reference and the device's "
+                                 "read-all-then-write differ); use ring > keyframe_index - 1")
         dev = self.counts.device
         kf = torch.zeros(2, dtype=torch.int32, device=dev) if kf is None else kf
         mag = torch.zeros(2, dtype=torch.float32, device=dev) if mag is None else mag
@@ -149,12 +174,8 @@ class DevicePatchGraph:
         # per-frame rows: patches [N*M, 3, P, P] moves M patches per frame
         fr = [poses, patches.view(patches.shape[0] // M, -1), intrinsics] + ([tstamps] if tstamps is not None else []) + list(frames)
         rg = [0, 0, 0] + ([0] if tstamps is not None else []) + [int(r) for r in rings]
-        if len(frames) != len(rings):
-            raise ValueError("one ring size per frame array")
         dl = dt = dc = None
         if delta is not None:
-            if tstamps is None:
-                raise ValueError("the delta log needs tstamps")
             dl, dt, dc = delta
         self._ext.kf_shift(kf, int(M), st, a["ii"], a["jj"], a["kk"], self.counts, fr, rg,
                            poses if dl is not None else None, tstamps if dl is not None else None,

@@ -586,7 +586,10 @@ int dpvo_ba_layer_backward(const void* poses, const void* patches, const void* i
    projective_ops.flow_mag (projective_ops.py:120-130, beta 0.5).  Writes
    kf = {drop, k = n - keyframe_index} and mag = {motionmag(i,j),
    motionmag(j,i)}.  No host synchronisation: kf predicates
-   dpvo_pg_remove_frame_dev and dpvo_kf_shift. */
+   dpvo_pg_remove_frame_dev and dpvo_kf_shift.
+   Limit: a drop moves keyframe_index - 1 frames and dpvo_kf_shift holds at
+   most 16 of them, so keyframe_index > 17 returns DPVO_ERR_UNSUPPORTED here,
+   before the decision that would predicate such a drop is launched. */
 int dpvo_kf_motion(const int64_t* ii, const int64_t* jj, const int64_t* kk, const int32_t* counts,
                    const float* poses, const float* patches, const float* intrinsics, int P,
                    const int32_t* st, int keyframe_index, double keyframe_thresh, int32_t* kf,
@@ -598,7 +601,14 @@ int dpvo_kf_motion(const int64_t* ii, const int64_t* jj, const int64_t* kk, cons
    k+1 .. n-1 of every frame array one row down (ring[a] > 0: row = frame %
    ring[a], the imap/gmap/fmap rings), then n -= 1, m -= M.  A drop whose
    pg.delta record finds the log full ORs 8 into counts[2] (the patch graph's
-   error word; the record is not kept). */
+   error word; the record is not kept).
+   Limits: narrays <= 12 (more: DPVO_ERR_UNSUPPORTED); the drop moves
+   keyframe_index - 1 <= 16 frames (dpvo_kf_motion refuses a larger index);
+   every ring[a] is 0 or > keyframe_index - 1.  Each 4-byte word (or byte) of
+   the moved rows is read for all frames and then written, which equals the
+   reference's frame-by-frame copy only while the moved rows do not wrap onto
+   each other; this entry does not know keyframe_index, the caller checks
+   (DevicePatchGraph.keyframe does). */
 int dpvo_kf_shift(const int32_t* kf, int M, int32_t* st, int64_t* ii, int64_t* jj, int64_t* kk,
                   int32_t* counts, int max_edges, void* const* frame_arrays,
                   const int64_t* bytes_per_frame, const int32_t* ring, int narrays,
@@ -613,7 +623,10 @@ int dpvo_kf_shift(const int32_t* kf, int M, int32_t* st, int64_t* ii, int64_t* j
    dpvo_pg_append_dev.  work: dpvo_edges_loop_work_floats() floats.
    Limits: (global_opt_freq - keyframe_index) x min(n_cap - removal_window,
    max_edge_age) <= 16384, n_cap x (global_opt_freq - keyframe_index) <=
-   131072, max_num_edges <= 1024.  A device n above n_cap takes no loop edges
+   131072, max_num_edges <= 1024 (else DPVO_ERR_UNSUPPORTED).  The target frames
+   [n - global_opt_freq, n - keyframe_index) must be frames for every
+   n > removal_window: keyframe_index >= 0 and global_opt_freq <=
+   removal_window + 1 (else DPVO_ERR_INVALID).  A device n above n_cap takes no loop edges
    and ORs 4 into *errors (optional; the patch graph's counts[2]). */
 int dpvo_edges_loop(const float* poses, const float* patches, const float* intrinsics,
                     const int64_t* ix, int P, int M, const int32_t* st, int n_cap,

@@ -17,45 +17,9 @@ import pytest
 import torch
 
 import oracle
+from keyframe_cases import _edges, _loop_scene, _scene
 
 pytestmark = pytest.mark.gpu
-
-
-def _quat(axis, ang):
-    axis = np.asarray(axis, np.float64)
-    axis = axis / np.linalg.norm(axis)
-    return np.concatenate([np.sin(ang / 2) * axis, [np.cos(ang / 2)]])
-
-
-def _scene(rng, N, M, P, motion, n):
-    """poses (world->camera, lietorch [t, q]) along x with step `motion`,
-    small rotations; patches inside a 160 x 120 image with inverse depth in
-    [0.2, 1]."""
-    poses = np.zeros((N, 7), np.float32)
-    for f in range(N):
-        q = _quat(rng.normal(size=3), 0.01 * rng.normal())
-        poses[f, :3] = [-motion[f] if f < n else 0.0, 0.01 * rng.normal(), 0.01 * rng.normal()]
-        poses[f, 3:] = q
-    pts = np.zeros((N * M, 3, P, P), np.float32)
-    cx = rng.uniform(10, 150, N * M)
-    cy = rng.uniform(10, 110, N * M)
-    off = np.arange(P) - P // 2
-    pts[:, 0] = cx[:, None, None] + off[None, None, :]
-    pts[:, 1] = cy[:, None, None] + off[None, :, None]
-    pts[:, 2] = rng.uniform(0.2, 1.0, N * M)[:, None, None]
-    intr = np.tile(np.array([100.0, 100.0, 80.0, 60.0], np.float32), (N, 1))
-    return poses, pts, intr
-
-
-def _edges(n, M, r=3):
-    ii, jj, kk = [], [], []
-    for a in range(n):
-        for b in range(max(0, a - r), min(n, a + r + 1)):
-            for m in range(M):
-                ii.append(a)
-                jj.append(b)
-                kk.append(a * M + m)
-    return np.array(ii, np.int64), np.array(jj, np.int64), np.array(kk, np.int64)
 
 
 @pytest.mark.parametrize("drop", [True, False])
@@ -127,24 +91,6 @@ def test_keyframe_frame_drop_matches_restatement(gpu, drop):
         t1, t0, dp = info["delta"]
         assert log[1][0].cpu().tolist() == [t1, t0]
         np.testing.assert_array_equal(log[0][0].cpu().numpy(), dp)
-
-
-def _loop_scene(rng, N, M, P, n, period=40):
-    """a camera circling with `period` frames per lap: frame pairs one lap
-    apart see the same view (small flow), others do not."""
-    poses = np.zeros((N, 7), np.float32)
-    for f in range(N):
-        th = 2 * np.pi * f / period
-        R = _quat([0, 1, 0], -th)
-        c = np.array([0.6 * np.sin(th), 0.0, 0.6 * (1 - np.cos(th))])
-        # world->camera: t = -R c (rotation about y applied to the centre)
-        ca, sa = np.cos(-th), np.sin(-th)
-        Rm = np.array([[ca, 0, sa], [0, 1, 0], [-sa, 0, ca]])
-        poses[f, :3] = -Rm @ c + 0.002 * rng.normal(size=3)
-        poses[f, 3:] = R
-    _, pts, intr = _scene(rng, N, M, P, np.zeros(N), 0)
-    pts[:, 2] = rng.uniform(0.5, 1.5, N * M)[:, None, None]
-    return poses, pts, intr
 
 
 @pytest.mark.parametrize("M,n,thresh", [(10, 120, 64.0), (96, 90, 64.0), (12, 200, 8.0)])
