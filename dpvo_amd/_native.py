@@ -67,6 +67,8 @@ def c_abi():
         _lib.dpvo_update_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_packed_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_encoder_saved_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_encoder_backward_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_trajectory_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 

@@ -1,6 +1,8 @@
 // encoder.hip -- DPVO's feature encoders (dpvo/extractor.py:200-264,
 // `BasicEncoder4`, the fnet / inet of net.py's Patchifier) as implicit-GEMM
-// convolutions on the gfx950 matrix cores.  Inference only.
+// convolutions on the gfx950 matrix cores: the inference forward, the training
+// forward that keeps its planes, and the device pack.  The backward is
+// encoder_bwd.hip.
 //
 // An encoder is eleven convolutions (all with bias):
 //
@@ -48,39 +50,43 @@
 //              16-B unit ((n / 16) KS + k / KK) 64 + 16 ((k % KK) / KQ) + n % 16,
 //              slot k % KQ (KK = 32 halves or 16 floats)
 //   biases     fp32, convs 0..10
+// dpvo_encoder_pack_weights_device (k_pack, one launch, one 4-byte word per
+// thread) writes the same bytes from device parameters.
+//
+// Saved buffer (dpvo_encoder_forward_train; carved in encoder_layout.hpp).  The
+// training forward is the launches above with every destination a plane of its
+// own, so the output is bit-identical to the inference forward.  Channels-last
+// fp32 planes, each rounded up to 256 B, in this order:
+//   'instance'  y0..y4 [n, H1, W1, 32] raw outputs of convs 0..4, then the
+//               outputs of layer1.0 and layer1.1; y5..y9 [n, H2, W2, 64] raw
+//               outputs of convs 5..9, then the outputs of layer2.0 and
+//               layer2.1; the statistic partials (scratch of the forward);
+//               ten (mean, rstd) sets, conv i at set i, [n, Cout, 2] each in a
+//               slot of n 64 2 floats
+//   'none'      o0..o4 [n, H1, W1, 32] and o5..o9 [n, H2, W2, 64]: the
+//               post-epilogue outputs of convs 0..9 (o2, o4, o6, o9 are the
+//               block outputs; o7 is the skip conv, no ReLU).  out > 0 is the
+//               mask of relu(conv) and of the block's outer ReLU.
 #include <string.h>
 
-#include "common.hpp"
+#include "encoder_layout.hpp"
 
 namespace dpvo {
 namespace {
 
-constexpr int kConvs = 11;
+using namespace enc;
+
 constexpr int kHdr = 256;
 constexpr int kThreads = 256, kWaves = 4;
-constexpr float kInEps = 1e-5f;
-constexpr int kK0 = 147, kK0Pad = 160;
 
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-struct ConvShape { int cin, cout, kh, stride; };
-inline ConvShape conv_shape(int ci, int out_dim) {
-  switch (ci) {
-    case 0: return {3, 32, 7, 2};
-    case 1: case 2: case 3: case 4: return {32, 32, 3, 1};
-    case 5: return {32, 64, 3, 2};
-    case 7: return {32, 64, 1, 2};
-    case 10: return {64, out_dim, 1, 1};
-    default: return {64, 64, 3, 1};
-  }
-}
 inline int conv_kpad(int ci, int out_dim) {
   const ConvShape s = conv_shape(ci, out_dim);
   return ci == 0 ? kK0Pad : s.kh * s.kh * s.cin;
 }
 inline size_t esize(int wdtype) { return wdtype == DPVO_F16 ? 2 : 4; }
-inline bool out_dim_ok(int d) { return d >= 64 && d <= 1024 && d % 64 == 0; }
 inline size_t w_off(int ci, int out_dim, size_t es) {
   size_t o = kHdr;
   for (int i = 0; i < ci; i++) o += es * conv_shape(i, out_dim).cout * conv_kpad(i, out_dim);
@@ -95,8 +101,6 @@ inline size_t blob_bytes(int out_dim, int wdtype) {
   return (b_off(kConvs, out_dim, esize(wdtype)) + 255) & ~(size_t)255;
 }
 
-inline int down(int n) { return (n - 1) / 2 + 1; }
-
 // --- workspace -------------------------------------------------------------------
 // three channels-last fp32 planes at half resolution (32 channels), three at
 // quarter resolution (64), the statistic partials and the ten (mean, rstd) sets
@@ -106,8 +110,6 @@ struct Ws {
   double* part;
   float* stat;
 };
-inline size_t r256(size_t n) { return (n + 255) & ~(size_t)255; }
-inline size_t max_parts(int H1, int W1) { return (size_t)((H1 + 3) / 4) * ((W1 + 15) / 16); }
 inline size_t ws_bytes(int n, int H, int W) {
   const int H1 = down(H), W1 = down(W), H2 = down(H1), W2 = down(W1);
   return 3 * r256((size_t)n * H1 * W1 * 32 * 4) + 3 * r256((size_t)n * H2 * W2 * 64 * 4) +
@@ -457,8 +459,6 @@ __global__ __launch_bounds__(256) void k_residual(const float* skip, const float
 }
 
 // --- host ---------------------------------------------------------------------------
-struct Dims { int n, H, W, H1, W1, H2, W2; };
-
 template <typename WT>
 struct Runner {
   const char* blob;
@@ -549,10 +549,49 @@ struct Runner {
     }
     return launch_status();
   }
+
+  // The training forward: the same launches with every destination a plane of
+  // its own inside `s` (encoder_layout.hpp), so the backward finds them.
+  // w.part / w.stat point into `s` too.
+  int run_train(const float* images, float* out, int nchw, const Saved& s) {
+    const int H = d.H, Wd = d.W, H1 = d.H1, W1 = d.W1, H2 = d.H2, W2 = d.W2;
+    float* const* h = s.h;
+    float* const* q = s.q;
+    if (instance) {
+      conv<7, 2, 3, 32, 1>(0, images, -1, H, Wd, H1, W1, h[0], 0, false, nullptr);
+      conv<3, 1, 32, 32, 2>(1, h[0], 0, H1, W1, H1, W1, h[1], 1, false, nullptr);
+      conv<3, 1, 32, 32, 2>(2, h[1], 1, H1, W1, H1, W1, h[2], 2, false, nullptr);
+      residual(h[0], 0, 2, h[2], 2, H1, W1, 32, h[5]);                     // layer1.0
+      conv<3, 1, 32, 32, 2>(3, h[5], -1, H1, W1, H1, W1, h[3], 3, false, nullptr);
+      conv<3, 1, 32, 32, 2>(4, h[3], 3, H1, W1, H1, W1, h[4], 4, false, nullptr);
+      residual(h[5], -1, 0, h[4], 4, H1, W1, 32, h[6]);                    // layer1.1
+      conv<3, 2, 32, 64, 1>(5, h[6], -1, H1, W1, H2, W2, q[0], 5, false, nullptr);
+      conv<3, 1, 64, 64, 1>(6, q[0], 5, H2, W2, H2, W2, q[1], 6, false, nullptr);
+      conv<1, 2, 32, 64, 1>(7, h[6], -1, H1, W1, H2, W2, q[2], 7, false, nullptr);
+      residual(q[2], 7, 1, q[1], 6, H2, W2, 64, q[5]);                     // layer2.0
+      conv<3, 1, 64, 64, 1>(8, q[5], -1, H2, W2, H2, W2, q[3], 8, false, nullptr);
+      conv<3, 1, 64, 64, 1>(9, q[3], 8, H2, W2, H2, W2, q[4], 9, false, nullptr);
+      residual(q[5], -1, 0, q[4], 9, H2, W2, 64, q[6]);                    // layer2.1
+      final_conv(q[6], out, nchw);
+    } else {
+      conv<7, 2, 3, 32, 1>(0, images, -1, H, Wd, H1, W1, h[0], -1, true, nullptr);
+      conv<3, 1, 32, 32, 2>(1, h[0], -1, H1, W1, H1, W1, h[1], -1, true, nullptr);
+      conv<3, 1, 32, 32, 2>(2, h[1], -1, H1, W1, H1, W1, h[2], -1, false, h[0]);  // layer1.0
+      conv<3, 1, 32, 32, 2>(3, h[2], -1, H1, W1, H1, W1, h[3], -1, true, nullptr);
+      conv<3, 1, 32, 32, 2>(4, h[3], -1, H1, W1, H1, W1, h[4], -1, false, h[2]);  // layer1.1
+      conv<3, 2, 32, 64, 1>(5, h[4], -1, H1, W1, H2, W2, q[0], -1, true, nullptr);
+      conv<1, 2, 32, 64, 1>(7, h[4], -1, H1, W1, H2, W2, q[2], -1, false, nullptr);
+      conv<3, 1, 64, 64, 1>(6, q[0], -1, H2, W2, H2, W2, q[1], -1, false, q[2]);  // layer2.0
+      conv<3, 1, 64, 64, 1>(8, q[1], -1, H2, W2, H2, W2, q[3], -1, true, nullptr);
+      conv<3, 1, 64, 64, 1>(9, q[3], -1, H2, W2, H2, W2, q[4], -1, false, q[1]);  // layer2.1
+      final_conv(q[4], out, nchw);
+    }
+    return launch_status();
+  }
 };
 
-// RNE float -> half bits on the host
-uint16_t half_bits(float f) {
+// RNE float -> half bits (host pack and device pack: one definition)
+__host__ __device__ inline uint16_t half_bits(float f) {
   uint32_t x;
   memcpy(&x, &f, 4);
   const uint32_t sign = (x >> 16) & 0x8000u;
@@ -574,10 +613,50 @@ uint16_t half_bits(float f) {
   return (uint16_t)(sign | h);
 }
 
-bool dims_ok(int n, int H, int W) {
-  // grid limits and 32-bit pixel counts
-  return n <= 65535 && H <= 65536 && W <= 65536 &&
-         (size_t)n * down(H) * down(W) <= (size_t)0x7fffffff / 64;
+// The packed blob written on the device, one 4-byte word per thread: the
+// inverse of the host pack's index map, so the bytes are the same.
+struct PackArgs {
+  const float* w[kConvs];
+  const float* b[kConvs];
+  int woff[kConvs + 1];  // first word of each conv's weights; [kConvs]: of the biases
+  int boff[kConvs + 1];  // first word of each conv's bias; [kConvs]: of the zero tail
+  int cin[kConvs], taps[kConvs], ks[kConvs];
+  int wdtype, out_dim, norm, words;
+};
+
+__device__ inline float pack_elem(const PackArgs& a, int ci, int slot, int KK, int KQ) {
+  const int unit = slot / KQ, kslot = slot % KQ, KS = a.ks[ci];
+  const int n16 = unit / (KS * 64), rem = unit % (KS * 64), u = rem % 64;
+  const int k = (rem / 64) * KK + (u / 16) * KQ + kslot, n = n16 * 16 + u % 16;
+  const int cin = a.cin[ci], taps = a.taps[ci];
+  if (k >= taps * cin) return 0.f;  // conv 0's padded K tail
+  return a.w[ci][((size_t)n * cin + k % cin) * taps + k / cin];
+}
+
+__global__ __launch_bounds__(256) void k_pack(PackArgs a, uint32_t* __restrict__ blob) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.words) return;
+  uint32_t v = 0;
+  if (i < kHdr / 4) {
+    v = i == 0 ? 0x31434e45u : i == 1 ? (uint32_t)a.wdtype : i == 2 ? (uint32_t)a.out_dim
+        : i == 3 ? (uint32_t)a.norm : 0u;
+  } else if (i < a.woff[kConvs]) {
+    int ci = 0;
+    while (i >= a.woff[ci + 1]) ci++;
+    const int wi = i - a.woff[ci];
+    if (a.wdtype == DPVO_F16) {
+      const uint32_t lo = half_bits(pack_elem(a, ci, 2 * wi, 32, 8));
+      const uint32_t hi = half_bits(pack_elem(a, ci, 2 * wi + 1, 32, 8));
+      v = lo | hi << 16;
+    } else {
+      v = __builtin_bit_cast(uint32_t, pack_elem(a, ci, wi, 16, 4));
+    }
+  } else if (i < a.boff[kConvs]) {
+    int ci = 0;
+    while (i >= a.boff[ci + 1]) ci++;
+    v = __builtin_bit_cast(uint32_t, a.b[ci][i - a.boff[ci]]);
+  }
+  blob[i] = v;
 }
 
 }  // namespace
@@ -651,4 +730,69 @@ DPVO_EXPORT int dpvo_encoder_forward(const void* blob, int wdtype, int norm, int
   Runner<float> r{(const char*)blob, out_dim, norm == DPVO_ENCODER_NORM_INSTANCE, d, ws,
                   as_stream(stream)};
   return r.run(images, out, nchw);
+}
+
+DPVO_EXPORT int dpvo_encoder_pack_weights_device(const float* const* params, int out_dim, int norm,
+                                                 int wdtype, void* blob, size_t blob_size,
+                                                 void* stream) {
+  if (!params || !blob) return DPVO_ERR_INVALID;
+  for (int i = 0; i < 2 * kConvs; i++)
+    if (!params[i]) return DPVO_ERR_INVALID;
+  if (!out_dim_ok(out_dim) || (wdtype != DPVO_F32 && wdtype != DPVO_F16) || !norm_ok(norm))
+    return DPVO_ERR_UNSUPPORTED;
+  if (blob_size < blob_bytes(out_dim, wdtype)) return DPVO_ERR_WORKSPACE;
+  const size_t es = esize(wdtype);
+  PackArgs a{};
+  for (int ci = 0; ci < kConvs; ci++) {
+    const ConvShape s = conv_shape(ci, out_dim);
+    a.w[ci] = params[2 * ci];
+    a.b[ci] = params[2 * ci + 1];
+    a.woff[ci] = (int)(w_off(ci, out_dim, es) / 4);
+    a.boff[ci] = (int)(b_off(ci, out_dim, es) / 4);
+    a.cin[ci] = s.cin;
+    a.taps[ci] = s.kh * s.kh;
+    a.ks[ci] = conv_kpad(ci, out_dim) / (wdtype == DPVO_F16 ? 32 : 16);
+  }
+  a.woff[kConvs] = (int)(w_off(kConvs, out_dim, es) / 4);
+  a.boff[kConvs] = (int)(b_off(kConvs, out_dim, es) / 4);
+  a.wdtype = wdtype;
+  a.out_dim = out_dim;
+  a.norm = norm;
+  a.words = (int)(blob_bytes(out_dim, wdtype) / 4);
+  hipLaunchKernelGGL(k_pack, dim3((a.words + 255) / 256), dim3(256), 0, as_stream(stream), a,
+                     (uint32_t*)blob);
+  return launch_status();
+}
+
+DPVO_EXPORT size_t dpvo_encoder_saved_bytes(int n_images, int H, int W, int out_dim, int norm) {
+  if (n_images < 1 || H < 1 || W < 1 || !out_dim_ok(out_dim) || !norm_ok(norm) ||
+      !dims_ok(n_images, H, W))
+    return 0;
+  return saved_bytes(make_dims(n_images, H, W), norm == DPVO_ENCODER_NORM_INSTANCE);
+}
+
+DPVO_EXPORT int dpvo_encoder_forward_train(const void* blob, int wdtype, int norm, int out_dim,
+                                           const float* images, int n_images, int H, int W,
+                                           float* out, int out_layout, void* saved,
+                                           size_t saved_size, void* stream) {
+  if (!blob || !images || !out || !saved || n_images < 1 || H < 1 || W < 1)
+    return DPVO_ERR_INVALID;
+  if (out_layout != DPVO_ENCODER_NCHW && out_layout != DPVO_ENCODER_NHWC) return DPVO_ERR_INVALID;
+  if ((wdtype != DPVO_F32 && wdtype != DPVO_F16) || !out_dim_ok(out_dim) || !norm_ok(norm) ||
+      !dims_ok(n_images, H, W))
+    return DPVO_ERR_UNSUPPORTED;
+  const bool instance = norm == DPVO_ENCODER_NORM_INSTANCE;
+  const Dims d = make_dims(n_images, H, W);
+  if (saved_size < saved_bytes(d, instance)) return DPVO_ERR_WORKSPACE;
+  const Saved s = saved_carve(saved, d, instance);
+  Ws ws{};
+  ws.part = s.part;
+  ws.stat = s.stat;
+  const int nchw = out_layout == DPVO_ENCODER_NCHW;
+  if (wdtype == DPVO_F16) {
+    Runner<__half> r{(const char*)blob, out_dim, instance, d, ws, as_stream(stream)};
+    return r.run_train(images, out, nchw, s);
+  }
+  Runner<float> r{(const char*)blob, out_dim, instance, d, ws, as_stream(stream)};
+  return r.run_train(images, out, nchw, s);
 }

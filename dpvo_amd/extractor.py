@@ -2,11 +2,12 @@
 
 ``BasicEncoder4`` has the reference module's parameter names, so a DPVO
 checkpoint's ``patchify.fnet.*`` / ``patchify.inet.*`` keys load unchanged; the
-forward pass is the implicit-GEMM HIP encoder of csrc/encoder.hip (inference
-only) and already includes Patchifier's ``/ 4``.  The parameters stay fp32
-tensors; ``dtype`` chooses how they are packed for the matrix cores:
-``torch.float16`` (fp16 operands, fp32 accumulation) or ``torch.float32``
-(exact fp32 products).
+forward pass is the implicit-GEMM HIP encoder of csrc/encoder.hip and already
+includes Patchifier's ``/ 4``.  The parameters stay fp32 tensors; ``dtype``
+chooses how they are packed for the matrix cores: ``torch.float16`` (fp16
+operands, fp32 accumulation) or ``torch.float32`` (exact fp32 products).
+With ``differentiable=True`` (fp32 only) the forward keeps its planes and the
+HIP backward of csrc/encoder_bwd.hip gives the gradients of the 22 parameters.
 """
 from __future__ import annotations
 
@@ -42,16 +43,74 @@ class _ResidualBlock(nn.Module):  # extractor.py:6-55 (parameters only)
                                                       stride=stride))
 
 
+class _EncoderFunction(torch.autograd.Function):
+    """forward_train + backward of one encoder.  Inputs: the module, the images
+    [N, 3, H, W] (contiguous fp32, no gradient), the output memory format and
+    the 22 parameters.  The blob is packed on the device from the parameters'
+    current values and ``saved`` is allocated per call, so neither an
+    optimiser step nor a second forward before the backward disturbs it.  No
+    host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, enc, x, fmt, *params):
+        e = ext()
+        dev = x.device
+        N, _, H, W = x.shape
+        ps = [p.detach().contiguous() for p in params]
+        blob = torch.empty(e.packed_bytes(enc.output_dim, e.F32), dtype=torch.uint8, device=dev)
+        e.pack_weights_device(ps, enc.output_dim, enc._ncode(), e.F32, blob)
+        need = e.saved_bytes(N, H, W, enc.output_dim, enc._ncode())
+        if need <= 0:
+            raise ValueError(f"BasicEncoder4: unsupported size {N} x {H} x {W}")
+        saved = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(N, enc.output_dim, out_size(out_size(H)), out_size(out_size(W)),
+                          dtype=torch.float32, device=dev, memory_format=fmt)
+        e.forward_train(blob, e.F32, enc._ncode(), x, out, saved)
+        ctx.enc = enc
+        ctx.saved = saved
+        ctx.save_for_backward(x, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        e = ext()
+        enc = ctx.enc
+        x, *params = ctx.saved_tensors
+        N, _, H, W = x.shape
+        if not (grad_out.is_contiguous()
+                or grad_out.is_contiguous(memory_format=torch.channels_last)):
+            grad_out = grad_out.contiguous()
+        ps = [p.detach().contiguous() for p in params]
+        grads = [torch.empty_like(p) for p in ps]
+        ws = torch.empty(e.backward_workspace_bytes(N, H, W, enc.output_dim), dtype=torch.uint8,
+                         device=x.device)
+        e.backward(enc._ncode(), ps, x, ctx.saved, grad_out.to(torch.float32), grads, ws)
+        return (None, None, None) + tuple(grads)
+
+
 class BasicEncoder4(nn.Module):
-    """Drop-in for ``dpvo.extractor.BasicEncoder4`` (inference) with
-    ``norm_fn`` 'instance' or 'none'.
+    """Drop-in for ``dpvo.extractor.BasicEncoder4`` with ``norm_fn``
+    'instance' or 'none'.
 
     forward(images [b, n, 3, H, W], channels_last=False) -> [b, n, output_dim,
     h, w] float32, **already divided by 4** (net.py:361-362); with
     ``channels_last`` the same values in channels-last memory.
+
+    ``differentiable=False`` (default): inference, under ``no_grad``.
+    ``differentiable=True`` (``dtype`` must be ``torch.float32``): when grad
+    mode is on and a parameter requires grad, the output carries gradients to
+    the 22 parameters (same values, bit for bit, as the inference path).  The
+    images get no gradient (``images.requires_grad`` raises ``ValueError``).
+    With ``norm_fn='instance'`` the bias of every conv but ``conv2`` cancels
+    in the mean subtraction: its gradient is exact zero here, where torch's
+    autograd returns rounding noise.  The fp16 pack has no gradient because
+    it has no yardstick: the autograd of a restatement that rounds the
+    operands to fp16 differs from the exact gradient by up to 0.36 max|g| at
+    test sizes, so it cannot serve as a reference.
     """
 
-    def __init__(self, output_dim=128, norm_fn="instance", dtype=torch.float16):
+    def __init__(self, output_dim=128, norm_fn="instance", dtype=torch.float16,
+                 differentiable=False):
         super().__init__()
         if norm_fn not in ("instance", "none"):
             raise ValueError("BasicEncoder4: norm_fn is 'instance' or 'none'")
@@ -59,6 +118,10 @@ class BasicEncoder4(nn.Module):
             raise ValueError("BasicEncoder4: dtype (the packed weight type) is float16 or float32")
         if output_dim % 64 or not 64 <= output_dim <= 1024:
             raise ValueError("BasicEncoder4: output_dim is a multiple of 64 in [64, 1024]")
+        if differentiable and dtype != torch.float32:
+            raise ValueError("BasicEncoder4: differentiable=True needs dtype=torch.float32 "
+                             "(the fp16 pack has no gradient)")
+        self.differentiable = bool(differentiable)
         self.norm_fn = norm_fn
         self.output_dim = int(output_dim)
         self.wdtype = dtype
@@ -114,9 +177,17 @@ class BasicEncoder4(nn.Module):
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
-    @torch.no_grad()
     def forward(self, images, channels_last=False):
+        train = (self.differentiable and torch.is_grad_enabled()
+                 and any(p.requires_grad for p in self.parameters()))
+        with torch.set_grad_enabled(train):
+            return self._forward(images, channels_last, train)
+
+    def _forward(self, images, channels_last, train):
         require_gpu(images)
+        if train and images.requires_grad:
+            raise ValueError("BasicEncoder4: the image gradient is not provided "
+                             "(images.requires_grad must be False)")
         if images.dim() != 5 or images.shape[2] != 3:
             raise ValueError("BasicEncoder4: images must be [b, n, 3, H, W]")
         b, n, _, H, W = images.shape
@@ -126,10 +197,16 @@ class BasicEncoder4(nn.Module):
         x = images.reshape(b * n, 3, H, W).to(torch.float32).contiguous()
         h, w = out_size(out_size(H)), out_size(out_size(W))
         fmt = torch.channels_last if channels_last else torch.contiguous_format
-        out = torch.empty(b * n, self.output_dim, h, w, dtype=torch.float32, device=dev,
-                          memory_format=fmt)
-        ext().forward(self.packed(dev), self._wcode(), self._ncode(), x, out,
-                      self.workspace(b * n, H, W, dev))
+        if train:
+            params = list(self.parameters())
+            if len(params) != 22:
+                raise RuntimeError("BasicEncoder4: expected 22 parameter tensors")
+            out = _EncoderFunction.apply(self, x, fmt, *params)
+        else:
+            out = torch.empty(b * n, self.output_dim, h, w, dtype=torch.float32, device=dev,
+                              memory_format=fmt)
+            ext().forward(self.packed(dev), self._wcode(), self._ncode(), x, out,
+                          self.workspace(b * n, H, W, dev))
         if channels_last:  # [b, n, C, h, w] with the channels-last strides kept
             return out.permute(0, 2, 3, 1).reshape(b, n, h, w, self.output_dim).permute(0, 1, 4, 2, 3)
         return out.view(b, n, self.output_dim, h, w)

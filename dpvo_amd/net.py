@@ -156,13 +156,16 @@ class Patchifier(nn.Module):
     replaces the random draw when given.
     """
 
-    def __init__(self, patch_size=3, dtype=torch.float16):
+    def __init__(self, patch_size=3, dtype=torch.float16, differentiable=False):
         super().__init__()
         from .extractor import BasicEncoder4
 
         self.patch_size = patch_size
-        self.fnet = BasicEncoder4(output_dim=128, norm_fn="instance", dtype=dtype)
-        self.inet = BasicEncoder4(output_dim=DIM, norm_fn="none", dtype=dtype)
+        self.differentiable = bool(differentiable)
+        self.fnet = BasicEncoder4(output_dim=128, norm_fn="instance", dtype=dtype,
+                                  differentiable=differentiable)
+        self.inet = BasicEncoder4(output_dim=DIM, norm_fn="none", dtype=dtype,
+                                  differentiable=differentiable)
 
     @staticmethod
     def _image_gradient(images):  # net.py:351-357
@@ -172,9 +175,16 @@ class Patchifier(nn.Module):
         g = torch.sqrt(dx ** 2 + dy ** 2)
         return torch.nn.functional.avg_pool2d(g, 4, 4)
 
-    @torch.no_grad()
     def forward(self, images, patches_per_image=80, disps=None, centroid_sel_strat="RANDOM",
                 return_color=False, coords=None):
+        """With ``differentiable=True`` (and grad mode on) fmap, gmap and imap
+        carry gradients to the encoders' parameters; otherwise the whole call
+        runs under ``no_grad``."""
+        with torch.set_grad_enabled(self.differentiable and torch.is_grad_enabled()):
+            return self._forward(images, patches_per_image, disps, centroid_sel_strat,
+                                 return_color, coords)
+
+    def _forward(self, images, patches_per_image, disps, centroid_sel_strat, return_color, coords):
         from . import altcorr
 
         require_gpu(images)
@@ -227,12 +237,13 @@ class Patchifier(nn.Module):
 class VONet(nn.Module):
     """Container with ``dpvo.net.VONet``'s attribute names (net.py:426-434), so
     a DPVO checkpoint's ``patchify.*`` / ``update.*`` keys load unchanged.
-    ``dtype`` is the packed weight type of both modules."""
+    ``dtype`` is the packed weight type of both modules; ``differentiable``
+    goes to the patchifier's encoders (the update operator has no backward)."""
 
-    def __init__(self, dtype=torch.float16):
+    def __init__(self, dtype=torch.float16, differentiable=False):
         super().__init__()
         self.P = 3
-        self.patchify = Patchifier(self.P, dtype=dtype)
+        self.patchify = Patchifier(self.P, dtype=dtype, differentiable=differentiable)
         self.update = Update(p=self.P, dtype=dtype)
         self.DIM = DIM
         self.RES = 4

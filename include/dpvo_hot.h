@@ -883,7 +883,8 @@ int dpvo_update_forward(const void* blob, int wdtype, const void* net, const voi
 
 /* ---------------------------------------------------------------------------
    The feature encoders (replace BasicEncoder4, dpvo/extractor.py:200-264: the
-   fnet / inet of net.py's Patchifier).  Inference only.
+   fnet / inet of net.py's Patchifier): the inference forward, and further
+   down the training forward and the backward.
 
      x = relu(norm(conv1(img)))                 7x7 stride 2,  3 -> 32
      x = layer1(x)                              two residual blocks, 32 -> 32
@@ -942,6 +943,59 @@ size_t dpvo_encoder_workspace_bytes(int n_images, int H, int W, int out_dim);
 int dpvo_encoder_forward(const void* blob, int wdtype, int norm, int out_dim, const float* images,
                          int n_images, int H, int W, float* out, int out_layout, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* --- the encoders' training surface (csrc/encoder.hip, csrc/encoder_bwd.hip) ---
+   The gradients of the 22 parameters; the image gradient is not provided.
+   Exact fp32 (DPVO_F32 weights are what the backward differentiates; an fp16
+   pack has no gradient here), fixed-order fp64 sums wherever a sum spans
+   workgroups, no float atomics: two calls on the same state are bit-identical. */
+
+/* DEVICE pack: the blob of dpvo_encoder_pack_weights, byte for byte (header
+   and zero padding included), written by one launch on `stream` from `params`,
+   a host array of 22 device pointers (fp32, PyTorch layout, state_dict
+   order).  For the step after an optimiser update: no host round trip.  Null
+   pointers (a null entry included): DPVO_ERR_INVALID; a bad out_dim, norm or
+   wdtype: DPVO_ERR_UNSUPPORTED; blob_bytes too small: DPVO_ERR_WORKSPACE; all
+   before the launch. */
+int dpvo_encoder_pack_weights_device(const float* const* params, int out_dim, int norm, int wdtype,
+                                     void* blob, size_t blob_bytes, void* stream);
+
+/* Bytes of the `saved` buffer of dpvo_encoder_forward_train (every plane the
+   backward needs; layout: csrc/encoder_layout.hpp); 0 where
+   dpvo_encoder_workspace_bytes returns 0 or for a bad norm. */
+size_t dpvo_encoder_saved_bytes(int n_images, int H, int W, int out_dim, int norm);
+
+/* dpvo_encoder_forward with every intermediate plane kept in the caller-owned
+   `saved` instead of a ping-pong workspace: the same kernels and the same
+   arithmetic, so `out` is bit-identical to dpvo_encoder_forward in both
+   layouts.  Status rules as dpvo_encoder_forward (short `saved`:
+   DPVO_ERR_WORKSPACE). */
+int dpvo_encoder_forward_train(const void* blob, int wdtype, int norm, int out_dim,
+                               const float* images, int n_images, int H, int W, float* out,
+                               int out_layout, void* saved, size_t saved_bytes, void* stream);
+
+/* Bytes of the backward's device workspace; 0 where
+   dpvo_encoder_workspace_bytes returns 0. */
+size_t dpvo_encoder_backward_workspace_bytes(int n_images, int H, int W, int out_dim);
+
+/* The backward.  params: host array of the 22 device fp32 parameter tensors
+   (the masters, PyTorch layout, state_dict order; the values the forward's
+   blob was packed from).  images, saved: as given to / filled by
+   dpvo_encoder_forward_train with the same (norm, out_dim, n_images, H, W).
+   grad_out: the cotangent of `out`, fp32 [n_images, out_dim, h, w], stored
+   NCHW-contiguous or channels-last (grad_layout).  grads: host array of 22
+   device fp32 tensors shaped like params, every element overwritten.  With
+   DPVO_ENCODER_NORM_INSTANCE the bias of convs 0..9 cancels in the mean
+   subtraction: its gradient is identically zero and exact zeros are written.
+   66 (instance) or 56 (none) launches.  Null pointers (a null entry of params
+   or grads included), non-positive sizes, an unknown grad_layout:
+   DPVO_ERR_INVALID; a bad norm or out_dim, or sizes outside the index range:
+   DPVO_ERR_UNSUPPORTED; short workspace: DPVO_ERR_WORKSPACE; all checked
+   before any launch. */
+int dpvo_encoder_backward(int norm, int out_dim, const float* const* params, const float* images,
+                          int n_images, int H, int W, const void* saved, const float* grad_out,
+                          int grad_layout, float* const* grads, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
