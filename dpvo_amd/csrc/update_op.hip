@@ -1,5 +1,7 @@
 // update_op.hip -- DPVO's update operator (dpvo/net.py:175-339, `Update`) as
-// fused gfx950 kernels on the matrix cores.  Inference only.
+// fused gfx950 kernels on the matrix cores: the inference forward, the training
+// forward (the same launches, every plane the backward needs kept in `saved`,
+// update_layout.hpp) and the device pack.  The backward is update_bwd.hip.
 //
 // The operator is a residual stream x [E, 384] pushed through 19 linears of
 // width 384 (the first reads corr [E, K0]), four LayerNorms, two neighbour
@@ -40,16 +42,21 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "update_layout.hpp"
 
 namespace dpvo {
 namespace {
 
-constexpr int kD = 384;
+using upd::kD;
+using upd::kEps;
+using upd::Plan;
+using upd::plan_count;
+using upd::rows_bytes;
+using upd::ints_bytes;
 constexpr int kThreads = 512, kWaves = 8, kNT = 3;  // a wave owns 48 output columns
 constexpr int kXP = 388;                            // fp32 LDS row pitch (floats)
 constexpr int kLayers = 19, kLN = 4;
 constexpr int kHdr = 256;
-constexpr float kEps = 1e-3f;
 constexpr int kUpdateBigTileE = 4096;  // E from which the 32-row tile is used
 
 // GEMM layers and LayerNorms, blob order
@@ -78,30 +85,20 @@ constexpr int V_BIAS = 0, V_LN = kLayers * kD, V_DW = V_LN + kLN * 2 * kD, V_WW 
 
 // --- workspace -----------------------------------------------------------------
 // six [E, 384] fp32 arrays, then per grouping (kk, ij) six int arrays of E + 1
-struct Plan {
-  int *rep, *pos, *dense, *off, *size, *members;  // members[off[g] + pos] = edge; off[E]: count
-};
 struct Ws {
   float *xA, *xB, *F, *G, *Y, *HY;
   Plan p[2];
 };
-inline size_t rows_bytes(int E) { return ((size_t)E * kD * 4 + 255) & ~(size_t)255; }
-inline size_t ints_bytes(int E) { return ((size_t)(E + 2) * 4 + 255) & ~(size_t)255; }
 inline size_t ws_bytes(int E) { return 6 * rows_bytes(E) + 12 * ints_bytes(E); }
 inline Ws ws_carve(void* base, int E) {
   char* p = (char*)base;
   Ws w;
   float** f[6] = {&w.xA, &w.xB, &w.F, &w.G, &w.Y, &w.HY};
   for (auto q : f) { *q = (float*)p; p += rows_bytes(E); }
-  for (int g = 0; g < 2; g++) {
-    int** a[6] = {&w.p[g].rep, &w.p[g].pos, &w.p[g].dense, &w.p[g].off, &w.p[g].size,
-                  &w.p[g].members};
-    for (auto q : a) { *q = (int*)p; p += ints_bytes(E); }
-  }
+  upd::carve_plans(p, E, w.p);
   return w;
 }
-// the group count of a plan lives on the device at off[E + 1]
-__device__ __forceinline__ int plan_count(const int* off, int E) { return off[E + 1]; }
+// the group count of a plan lives on the device at off[E + 1] (plan_count)
 
 // --- group plan ------------------------------------------------------------------
 // rep[e]: smallest edge with e's id; pos[e]: how many smaller edges share it.
@@ -195,10 +192,16 @@ __global__ __launch_bounds__(1024) void k_plan_build(int E, Plan p0, Plan p1) {
 // Y[g][c] = sum_m softmax_m(G[m][c]) F[m][c] over the members m of group g in
 // ascending edge order, with the per-(group, channel) maximum subtracted
 // (torch_scatter.scatter_softmax).  One workgroup per group, a thread per channel.
+// TRAIN: the rows of Y past the group count are zeroed (the backward's GEMMs
+// read all E rows).
+template <bool TRAIN>
 __global__ __launch_bounds__(kD) void k_agg(const float* __restrict__ F, const float* __restrict__ Gv,
                                             Plan p, int E, float* __restrict__ Y) {
   const int g = blockIdx.x;
-  if (g >= plan_count(p.off, E)) return;
+  if (g >= plan_count(p.off, E)) {
+    if constexpr (TRAIN) Y[(size_t)g * kD + threadIdx.x] = 0.f;
+    return;
+  }
   const int c = threadIdx.x, b = p.off[g], e = p.off[g + 1];
   float m = -INFINITY;
   for (int i = b; i < e; i++) m = fmaxf(m, Gv[(size_t)p.members[i] * kD + c]);
@@ -463,12 +466,25 @@ __device__ __forceinline__ void emit_fg(const float* X, const Blob& B, int lf, f
   const int row0 = blockIdx.x * 16 * MT;                                 \
   (void)tmp; (void)TP; (void)KSD
 
+// What a training launch keeps on top of its outputs (planes of `saved`,
+// update_layout.hpp); unused by the inference instantiations.
+struct Keep {
+  float *a, *b, *c, *d, *e;
+  size_t stride;  // floats between consecutive planes of `saved`
+};
+template <int MT>
+__device__ __forceinline__ void keep(float* __restrict__ dst, int row0, int E, int row, int col,
+                                     float v) {
+  if (row0 + row < E) dst[(size_t)(row0 + row) * kD + col] = v;
+}
+
 // x = LN(net + inp + corr MLP(corr))           (net.py:283-284, 201-208)
-template <typename WT, int MT>
+// TRAIN keeps corr (a), A0 (b), Z2 (c), A3 (d), S0 (e).
+template <typename WT, int MT, bool TRAIN = false>
 __global__ __launch_bounds__(kThreads) void k_corr(Blob B, const void* __restrict__ net,
                                                    const void* __restrict__ inp,
                                                    const void* __restrict__ corr, int io16, int E,
-                                                   int K0, float* __restrict__ xout) {
+                                                   int K0, float* __restrict__ xout, Keep kp) {
   UPD_SMEM();
   f32x4 acc[MT][kNT];
   zero_acc<MT>(acc);
@@ -481,28 +497,38 @@ __global__ __launch_bounds__(kThreads) void k_corr(Blob B, const void* __restric
       // clamped address, value zeroed past E / K0: unconditional loads
       const float v = io_load(corr, (size_t)min(e, E - 1) * K0 + min(k, K0 - 1), io16);
       if (col < kc) tmp[row * TP + col] = to_w(e < E && k < K0 ? v : 0.f, WT{});
+      if constexpr (TRAIN)
+        if (col < kc && e < E && k < K0) kp.a[(size_t)e * K0 + k] = v;
     }
     __syncthreads();
     gemm<WT, MT, WT>(acc, tmp, TP, kc / KK, B.w(L_CORR0), KS0, c0 / KK);
     __syncthreads();
   }
-  epilogue<MT>(acc, B.bias(L_CORR0),
-               [&](int row, int col, float v) { X[row * kXP + col] = fmaxf(v, 0.f); });
+  epilogue<MT>(acc, B.bias(L_CORR0), [&](int row, int col, float v) {
+    X[row * kXP + col] = fmaxf(v, 0.f);
+    if constexpr (TRAIN) keep<MT>(kp.b, row0, E, row, col, fmaxf(v, 0.f));
+  });
   __syncthreads();
   zero_acc<MT>(acc);
   gemm<WT, MT, float>(acc, X, kXP, KSD, B.w(L_CORR2), KSD, 0);
   __syncthreads();
-  epilogue<MT>(acc, B.bias(L_CORR2), [&](int row, int col, float v) { X[row * kXP + col] = v; });
+  epilogue<MT>(acc, B.bias(L_CORR2), [&](int row, int col, float v) {
+    X[row * kXP + col] = v;
+    if constexpr (TRAIN) keep<MT>(kp.c, row0, E, row, col, v);
+  });
   __syncthreads();
   layer_norm<MT>(X, B.ln(N_CORR3), true);
   __syncthreads();
+  if constexpr (TRAIN) store_rows<MT>(X, kp.d, row0, E);
   zero_acc<MT>(acc);
   gemm<WT, MT, float>(acc, X, kXP, KSD, B.w(L_CORR5), KSD, 0);
   __syncthreads();
   epilogue<MT>(acc, B.bias(L_CORR5), [&](int row, int col, float v) {
     // rows past E take a copy of row E - 1 (never stored): unconditional loads
     const size_t o = (size_t)min(row0 + row, E - 1) * kD + col;
-    X[row * kXP + col] = io_load(net, o, io16) + io_load(inp, o, io16) + v;
+    const float s = io_load(net, o, io16) + io_load(inp, o, io16) + v;
+    X[row * kXP + col] = s;
+    if constexpr (TRAIN) keep<MT>(kp.e, row0, E, row, col, s);
   });
   __syncthreads();
   layer_norm<MT>(X, B.ln(N_NORM), false);
@@ -512,11 +538,12 @@ __global__ __launch_bounds__(kThreads) void k_corr(Blob B, const void* __restric
 
 // x_new = x + c(m * x[idx]) from x_old (double-buffered: xin is never written
 // here), optionally f/g of the first aggregation      (net.py:305-306, 179-187)
-template <typename WT, int MT, bool FG>
+// TRAIN keeps the hidden layer's post-activation (a).
+template <typename WT, int MT, bool FG, bool TRAIN = false>
 __global__ __launch_bounds__(kThreads) void k_nbr(Blob B, const float* __restrict__ xin,
                                                   const int64_t* __restrict__ idx, int E, int la,
                                                   float* __restrict__ xout, float* __restrict__ F,
-                                                  float* __restrict__ G) {
+                                                  float* __restrict__ G, Keep kp) {
   UPD_SMEM();
   load_rows<MT>(X, xin, row0, E, nullptr, nullptr);
   gather_rows<WT, MT>(tmp, xin, row0, E, idx, E);
@@ -527,6 +554,7 @@ __global__ __launch_bounds__(kThreads) void k_nbr(Blob B, const float* __restric
   __syncthreads();
   epilogue<MT>(acc, B.bias(la), [&](int row, int col, float v) {
     tmp[row * TP + col] = to_w(fmaxf(v, 0.f), WT{});
+    if constexpr (TRAIN) keep<MT>(kp.a, row0, E, row, col, fmaxf(v, 0.f));
   });
   __syncthreads();
   zero_acc<MT>(acc);
@@ -556,25 +584,33 @@ __global__ __launch_bounds__(kThreads) void k_h(Blob B, const float* __restrict_
 
 // x += HY[group]; f/g of the second aggregation        (net.py:319-320)
 template <typename WT, int MT>
-__global__ __launch_bounds__(kThreads) void k_addfg(Blob B, float* __restrict__ x,
+// (xout may be xin: a workgroup reads and writes its own rows only)
+__global__ __launch_bounds__(kThreads) void k_addfg(Blob B, const float* xin, float* xout,
                                                     const float* __restrict__ HY, Plan p, int E,
                                                     float* __restrict__ F, float* __restrict__ G) {
   UPD_SMEM();
-  load_rows<MT>(X, x, row0, E, HY, p.dense);
+  load_rows<MT>(X, xin, row0, E, HY, p.dense);
   __syncthreads();
-  store_rows<MT>(X, x, row0, E);  // own rows only
+  store_rows<MT>(X, xout, row0, E);  // own rows only
   emit_fg<WT, MT>(X, B, L_IJF, F, G, row0, E);
 }
 
 // x += HY[group]; gru; heads                            (net.py:320-326, 194-219)
-template <typename WT, int MT>
+// TRAIN keeps X4 (a), then per block S, A, R and the block's output, four
+// consecutive planes from b (b + 4 stride for the second block), and w (c).
+template <typename WT, int MT, bool TRAIN = false>
 __global__ __launch_bounds__(kThreads) void k_final(Blob B, const float* __restrict__ x,
                                                     const float* __restrict__ HY, Plan p, int E,
                                                     int io16, void* __restrict__ net_out,
-                                                    float* __restrict__ dout, float* __restrict__ wout) {
+                                                    float* __restrict__ dout, float* __restrict__ wout,
+                                                    Keep kp) {
   UPD_SMEM();
   load_rows<MT>(X, x, row0, E, HY, p.dense);
   __syncthreads();
+  if constexpr (TRAIN) {
+    store_rows<MT>(X, kp.a, row0, E);
+    __syncthreads();  // the LayerNorm below rewrites X
+  }
   f32x4 gate[MT][kNT], acc[MT][kNT];
 #pragma unroll 1
   for (int blk = 0; blk < 2; blk++) {
@@ -585,8 +621,11 @@ __global__ __launch_bounds__(kThreads) void k_final(Blob B, const float* __restr
     gemm<WT, MT, float>(gate, X, kXP, KSD, B.w(l0), KSD, 0);
     zero_acc<MT>(acc);
     gemm<WT, MT, float>(acc, X, kXP, KSD, B.w(l0 + 1), KSD, 0);
+    float* kb = nullptr;
+    if constexpr (TRAIN) kb = kp.b + (size_t)blk * 4 * kp.stride;
     epilogue<MT>(acc, B.bias(l0 + 1), [&](int row, int col, float v) {
       tmp[row * TP + col] = to_w(fmaxf(v, 0.f), WT{});
+      if constexpr (TRAIN) keep<MT>(kb + kp.stride, row0, E, row, col, fmaxf(v, 0.f));
     });
     __syncthreads();  // tmp complete; every read of X by the two GEMMs is done
     zero_acc<MT>(acc);
@@ -610,9 +649,17 @@ __global__ __launch_bounds__(kThreads) void k_final(Blob B, const float* __restr
             const int row = m * 16 + q * 4 + i, col = wave * 48 + n * 16 + r;
             const float s = 1.0f / (1.0f + expf(-(gate[m][n][i] + bgv[n])));
             X[row * kXP + col] += s * (acc[m][n][i] + brv[n]);
+            if constexpr (TRAIN) {
+              keep<MT>(kb, row0, E, row, col, s);
+              keep<MT>(kb + 2 * kp.stride, row0, E, row, col, acc[m][n][i] + brv[n]);
+            }
           }
     }
     __syncthreads();
+    if constexpr (TRAIN) {
+      store_rows<MT>(X, kb + 3 * kp.stride, row0, E);
+      __syncthreads();
+    }
   }
   // net_out, then the two heads on relu(x): a wave per row
   for (int i = threadIdx.x; i < 16 * MT * kD; i += kThreads) {
@@ -642,8 +689,30 @@ __global__ __launch_bounds__(kThreads) void k_final(Blob B, const float* __restr
       dout[2 * e + 1] = s[1] + V[V_DB + 1];
       wout[2 * e] = 1.0f / (1.0f + expf(-(s[2] + V[V_WB])));
       wout[2 * e + 1] = 1.0f / (1.0f + expf(-(s[3] + V[V_WB + 1])));
+      if constexpr (TRAIN) {
+        kp.c[2 * e] = wout[2 * e];
+        kp.c[2 * e + 1] = wout[2 * e + 1];
+      }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_copy_ints(const int* __restrict__ src,
+                                                   int* __restrict__ dst, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
+// the six ReLU masks of a training forward, uint8 [6, E, 384]
+__global__ __launch_bounds__(256) void k_relu_masks(const float* __restrict__ planes, size_t stride,
+                                                    int E, uint8_t* __restrict__ out) {
+  constexpr int which[6] = {upd::P_A0, upd::P_A3, upd::P_A1, upd::P_A2, upd::P_A4, upd::P_A5};
+  const size_t n = (size_t)E * kD, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int m = blockIdx.y;
+  const int pl = m == 0 ? which[0] : m == 1 ? which[1] : m == 2 ? which[2] : m == 3 ? which[3]
+                 : m == 4 ? which[4] : which[5];
+  out[(size_t)m * n + i] = planes[(size_t)pl * stride + i] > 0.f ? 1 : 0;
 }
 
 // --- host ---------------------------------------------------------------------------
@@ -671,31 +740,55 @@ bool ensure_lds(size_t lds) {
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(kThreads), lds, st, __VA_ARGS__);        \
   } while (0)
 
-template <typename WT, int MT>
+// TRAIN: the same launches with every intermediate written to a plane of
+// `saved` (x0..x3, f, g and the group rows directly, the on-chip ones through
+// Keep), then a copy of the two group plans.
+template <typename WT, int MT, bool TRAIN>
 int forward_t(const Blob& B, const void* net, const void* inp, const void* corr, const int64_t* ix,
-              const int64_t* jx, int E, int K0, int io16, const Ws& w, void* net_out, float* d,
-              float* wo, hipStream_t st) {
+              const int64_t* jx, int E, int K0, int io16, const Ws& w, const upd::Saved* sv,
+              void* net_out, float* d, float* wo, hipStream_t st) {
   constexpr size_t lds = lds_bytes<WT, MT>();
   const int tiles = (E + 16 * MT - 1) / (16 * MT);
-  UPD_LAUNCH((k_corr<WT, MT>), B, net, inp, corr, io16, E, K0, w.xA);
-  UPD_LAUNCH((k_nbr<WT, MT, false>), B, (const float*)w.xA, ix, E, (int)L_C1A, w.xB, w.F, w.G);
-  UPD_LAUNCH((k_nbr<WT, MT, true>), B, (const float*)w.xB, jx, E, (int)L_C2A, w.xA, w.F, w.G);
-  hipLaunchKernelGGL(k_agg, dim3(E), dim3(kD), 0, st, (const float*)w.F, (const float*)w.G, w.p[0],
-                     E, w.Y);
-  UPD_LAUNCH((k_h<WT, MT>), B, (const float*)w.Y, w.p[0], E, (int)L_KKH, w.HY);
-  UPD_LAUNCH((k_addfg<WT, MT>), B, w.xA, (const float*)w.HY, w.p[0], E, w.F, w.G);
-  hipLaunchKernelGGL(k_agg, dim3(E), dim3(kD), 0, st, (const float*)w.F, (const float*)w.G, w.p[1],
-                     E, w.Y);
-  UPD_LAUNCH((k_h<WT, MT>), B, (const float*)w.Y, w.p[1], E, (int)L_IJH, w.HY);
-  UPD_LAUNCH((k_final<WT, MT>), B, (const float*)w.xA, (const float*)w.HY, w.p[1], E, io16, net_out,
-             d, wo);
+  auto P = [&](int i) { return TRAIN ? sv->pl[i] : nullptr; };
+  float* x0 = TRAIN ? P(upd::P_X0) : w.xA;
+  float* x1 = TRAIN ? P(upd::P_X1) : w.xB;
+  float* x2 = TRAIN ? P(upd::P_X2) : w.xA;
+  float* x3 = TRAIN ? P(upd::P_X3) : w.xA;
+  float* F0 = TRAIN ? P(upd::P_FKK) : w.F, *G0 = TRAIN ? P(upd::P_GKK) : w.G;
+  float* F1 = TRAIN ? P(upd::P_FIJ) : w.F, *G1 = TRAIN ? P(upd::P_GIJ) : w.G;
+  float* Y0 = TRAIN ? P(upd::P_YKK) : w.Y, *Y1 = TRAIN ? P(upd::P_YIJ) : w.Y;
+  const size_t stride = rows_bytes(E) / 4;
+  Keep kc{}, k1{}, k2{}, kf{};
+  if (TRAIN) {
+    kc = Keep{sv->corr, P(upd::P_A0), P(upd::P_Z2), P(upd::P_A3), P(upd::P_S0), stride};
+    k1.a = P(upd::P_A1);
+    k2.a = P(upd::P_A2);
+    kf = Keep{P(upd::P_X4), P(upd::P_S1), sv->w, nullptr, nullptr, stride};
+  }
+  UPD_LAUNCH((k_corr<WT, MT, TRAIN>), B, net, inp, corr, io16, E, K0, x0, kc);
+  UPD_LAUNCH((k_nbr<WT, MT, false, TRAIN>), B, (const float*)x0, ix, E, (int)L_C1A, x1, F0, G0, k1);
+  UPD_LAUNCH((k_nbr<WT, MT, true, TRAIN>), B, (const float*)x1, jx, E, (int)L_C2A, x2, F0, G0, k2);
+  hipLaunchKernelGGL(k_agg<TRAIN>, dim3(E), dim3(kD), 0, st, (const float*)F0, (const float*)G0,
+                     w.p[0], E, Y0);
+  UPD_LAUNCH((k_h<WT, MT>), B, (const float*)Y0, w.p[0], E, (int)L_KKH, w.HY);
+  UPD_LAUNCH((k_addfg<WT, MT>), B, (const float*)x2, x3, (const float*)w.HY, w.p[0], E, F1, G1);
+  hipLaunchKernelGGL(k_agg<TRAIN>, dim3(E), dim3(kD), 0, st, (const float*)F1, (const float*)G1,
+                     w.p[1], E, Y1);
+  UPD_LAUNCH((k_h<WT, MT>), B, (const float*)Y1, w.p[1], E, (int)L_IJH, w.HY);
+  UPD_LAUNCH((k_final<WT, MT, TRAIN>), B, (const float*)x3, (const float*)w.HY, w.p[1], E, io16,
+             net_out, d, wo, kf);
+  if (TRAIN) {
+    // the plan arrays are contiguous in both buffers
+    const int n = (int)(12 * ints_bytes(E) / 4);
+    hipLaunchKernelGGL(k_copy_ints, dim3((n + 255) / 256), dim3(256), 0, st,
+                       (const int*)w.p[0].rep, sv->plan[0].rep, n);
+  }
   return launch_status();
 }
 
-// RNE float -> half bits on the host
-uint16_t half_bits(float f) {
-  uint32_t x;
-  memcpy(&x, &f, 4);
+// RNE float -> half bits, host and device (the device pack writes the host pack's bytes)
+__host__ __device__ inline uint16_t half_bits(float f) {
+  uint32_t x = __builtin_bit_cast(uint32_t, f);
   const uint32_t sign = (x >> 16) & 0x8000u;
   x &= 0x7fffffffu;
   if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0));
@@ -714,7 +807,7 @@ uint16_t half_bits(float f) {
   if (rem > 0x1000u || (rem == 0x1000u && (h & 1))) h++;
   return (uint16_t)(sign | h);
 }
-float half_value(uint16_t h) {
+__host__ __device__ inline float half_value(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
   uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu, x;
   if (e == 0) {
@@ -726,9 +819,7 @@ float half_value(uint16_t h) {
     }
   } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
   else x = sign | ((e + 112) << 23) | (m << 13);
-  float f;
-  memcpy(&f, &x, 4);
-  return f;
+  return __builtin_bit_cast(float, x);
 }
 
 // PyTorch state_dict order of Update (net.py:179-219): weight, bias pairs
@@ -738,7 +829,92 @@ constexpr int kLayerTensor[kLayers] = {38, 40, 44, 0, 2, 4, 6, 10, 12, 14, 16, 1
 constexpr int kLNTensor[kLN] = {8, 42, 22, 30};
 constexpr int kTensorDW = 46, kTensorWW = 48;
 
+// --- device pack ------------------------------------------------------------------------
+// blockIdx.y < 19: the weights of that layer, a 4-byte word per thread
+// (grid-stride); 19..49: one 384-float vector of the vectors section each;
+// 50: the header, the head biases and the zero tail.  The tensor a block reads
+// is block-uniform.
+struct PackArgs {
+  const float* t[upd::kTensors];
+  int wdtype, K0, K0p;
+  unsigned tail_words;  // words from the end of the vectors to the end of the blob
+};
+constexpr int kPackVecs = kLayers + 2 * kLN + 4;
+
+__device__ __forceinline__ float pack_elem(const float* __restrict__ W, int K, int KS, int KK,
+                                           int KQ, unsigned slot) {
+  const unsigned unit = slot / KQ, j = slot % KQ, u = unit % 64, blk = unit / 64;
+  const int n = (int)(blk / KS) * 16 + (int)(u % 16), k = (int)(blk % KS) * KK + (int)(u / 16) * KQ + j;
+  return k < K ? W[(size_t)n * K + k] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_pack(PackArgs a, uint32_t* __restrict__ blob) {
+  constexpr int lt[kLayers] = {38, 40, 44, 0, 2, 4, 6, 10, 12, 14, 16, 18, 20, 24, 26, 28, 32, 34, 36};
+  constexpr int lnt[kLN] = {8, 42, 22, 30};
+  const bool h16 = a.wdtype == DPVO_F16;
+  const Blob B{reinterpret_cast<const char*>(blob), a.K0p, h16 ? (size_t)2 : (size_t)4};
+  const int y = blockIdx.y;
+  if (y < kLayers) {
+    const int K = y == 0 ? a.K0 : kD, Kp = y == 0 ? a.K0p : kD;
+    const int KK = h16 ? 32 : 16, KQ = KK / 4, KS = Kp / KK;
+    const float* W = a.t[lt[y]];
+    uint32_t* out = blob + (reinterpret_cast<const char*>(B.w(y)) - B.base) / 4;
+    const unsigned words = (unsigned)kD * Kp / (h16 ? 2 : 1);
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) {
+      if (h16) {
+        const uint32_t lo = half_bits(pack_elem(W, K, KS, KK, KQ, 2 * i));
+        const uint32_t hi = half_bits(pack_elem(W, K, KS, KK, KQ, 2 * i + 1));
+        out[i] = lo | (hi << 16);
+      } else {
+        out[i] = __builtin_bit_cast(uint32_t, pack_elem(W, K, KS, KK, KQ, i));
+      }
+    }
+    return;
+  }
+  if (blockIdx.x != 0) return;
+  float* V = reinterpret_cast<float*>(blob) + (reinterpret_cast<const char*>(B.vec()) - B.base) / 4;
+  const int v = y - kLayers;
+  if (v < kPackVecs) {
+    const float* src;
+    float* dst;
+    bool round = false;
+    if (v < kLayers) {
+      src = a.t[lt[v] + 1];
+      dst = V + V_BIAS + v * kD;
+    } else if (v < kLayers + 2 * kLN) {
+      const int i = (v - kLayers) / 2, gb = (v - kLayers) % 2;
+      src = a.t[lnt[i] + gb];
+      dst = V + V_LN + i * 2 * kD + gb * kD;
+    } else {
+      const int h = v - kLayers - 2 * kLN;  // d.W rows 0, 1, then w.W rows 0, 1
+      src = a.t[h < 2 ? 46 : 48] + (h & 1) * kD;
+      dst = V + V_DW + h * kD;
+      round = h16;
+    }
+    for (int i = threadIdx.x; i < kD; i += 256)
+      dst[i] = round ? half_value(half_bits(src[i])) : src[i];
+    return;
+  }
+  for (int i = threadIdx.x; i < kHdr / 4; i += 256)
+    blob[i] = i == 0 ? 0x31445055u : i == 1 ? (uint32_t)a.wdtype : i == 2 ? (uint32_t)a.K0
+              : i == 3 ? (uint32_t)a.K0p : 0u;
+  if (threadIdx.x < 2) {
+    V[V_DB + threadIdx.x] = a.t[47][threadIdx.x];
+    V[V_WB + threadIdx.x] = a.t[49][threadIdx.x];
+  }
+  for (unsigned i = threadIdx.x; i < a.tail_words; i += 256) V[kVecFloats + i] = 0.f;
+}
+
 }  // namespace
+
+void upd::launch_plans(const int64_t* ids0, const int64_t* ids1, int E, const Plan& p0,
+                       const Plan& p1, hipStream_t st) {
+  hipLaunchKernelGGL(k_plan_init, dim3((E + 255) / 256), dim3(256), 0, st, E, p0, p1);
+  hipLaunchKernelGGL(k_plan_rank, dim3((E + 255) / 256, (E + kPlanChunk - 1) / kPlanChunk, 2),
+                     dim3(256), 0, st, ids0, ids1, E, p0, p1);
+  hipLaunchKernelGGL(k_plan_build, dim3(2), dim3(1024), 0, st, E, p0, p1);
+}
+
 }  // namespace dpvo
 
 using namespace dpvo;
@@ -801,11 +977,7 @@ DPVO_EXPORT int dpvo_update_plan(const int64_t* gk, const int64_t* gij, int E, v
   if (!gk || !gij || !workspace) return DPVO_ERR_INVALID;
   if (workspace_size < ws_bytes(E)) return DPVO_ERR_WORKSPACE;
   const Ws w = ws_carve(workspace, E);
-  hipLaunchKernelGGL(k_plan_init, dim3((E + 255) / 256), dim3(256), 0, as_stream(stream), E, w.p[0],
-                     w.p[1]);
-  hipLaunchKernelGGL(k_plan_rank, dim3((E + 255) / 256, (E + kPlanChunk - 1) / kPlanChunk, 2),
-                     dim3(256), 0, as_stream(stream), gk, gij, E, w.p[0], w.p[1]);
-  hipLaunchKernelGGL(k_plan_build, dim3(2), dim3(1024), 0, as_stream(stream), E, w.p[0], w.p[1]);
+  upd::launch_plans(gk, gij, E, w.p[0], w.p[1], as_stream(stream));
   return launch_status();
 }
 
@@ -832,8 +1004,73 @@ DPVO_EXPORT int dpvo_update_forward(const void* blob, int wdtype, const void* ne
   // LDS, but only one workgroup per CU then: measured slower)
   const bool big = E >= kUpdateBigTileE;
   if (wdtype == DPVO_F16)
-    return big ? forward_t<__half, 2>(B, net, inp, corr, ix, jx, E, K0, io16, ws, net_out, d, w, st)
-               : forward_t<__half, 1>(B, net, inp, corr, ix, jx, E, K0, io16, ws, net_out, d, w, st);
-  return big ? forward_t<float, 2>(B, net, inp, corr, ix, jx, E, K0, io16, ws, net_out, d, w, st)
-             : forward_t<float, 1>(B, net, inp, corr, ix, jx, E, K0, io16, ws, net_out, d, w, st);
+    return big ? forward_t<__half, 2, false>(B, net, inp, corr, ix, jx, E, K0, io16, ws, nullptr,
+                                             net_out, d, w, st)
+               : forward_t<__half, 1, false>(B, net, inp, corr, ix, jx, E, K0, io16, ws, nullptr,
+                                             net_out, d, w, st);
+  return big ? forward_t<float, 2, false>(B, net, inp, corr, ix, jx, E, K0, io16, ws, nullptr,
+                                          net_out, d, w, st)
+             : forward_t<float, 1, false>(B, net, inp, corr, ix, jx, E, K0, io16, ws, nullptr,
+                                          net_out, d, w, st);
+}
+
+DPVO_EXPORT int dpvo_update_pack_weights_device(const float* const* params, int dim, int K0,
+                                                int wdtype, void* blob, size_t blob_size,
+                                                void* stream) {
+  if (dim != kD || (wdtype != DPVO_F32 && wdtype != DPVO_F16)) return DPVO_ERR_UNSUPPORTED;
+  if (K0 < 1 || !params || !blob) return DPVO_ERR_INVALID;
+  for (int i = 0; i < upd::kTensors; i++)
+    if (!params[i]) return DPVO_ERR_INVALID;
+  if (blob_size < blob_bytes(K0, wdtype)) return DPVO_ERR_WORKSPACE;
+  PackArgs a{};
+  for (int i = 0; i < upd::kTensors; i++) a.t[i] = params[i];
+  a.wdtype = wdtype;
+  a.K0 = K0;
+  a.K0p = k0pad(K0);
+  a.tail_words =
+      (unsigned)((blob_bytes(K0, wdtype) - v_off(a.K0p, esize(wdtype)) - kVecFloats * 4) / 4);
+  const unsigned words = (unsigned)(kD * (size_t)a.K0p * esize(wdtype) / 4);
+  hipLaunchKernelGGL(k_pack, dim3((words + 255) / 256, kLayers + kPackVecs + 1), dim3(256), 0,
+                     as_stream(stream), a, (uint32_t*)blob);
+  return launch_status();
+}
+
+DPVO_EXPORT size_t dpvo_update_saved_bytes(int E, int K0) {
+  if (E < 1 || K0 < 1) return 0;
+  return upd::saved_bytes(E, K0);
+}
+
+DPVO_EXPORT int dpvo_update_forward_train(const void* blob, int wdtype, const void* net,
+                                          const void* inp, const void* corr, const int64_t* ix,
+                                          const int64_t* jx, int E, int dim, int K0, int iodtype,
+                                          void* workspace, size_t workspace_size, void* saved,
+                                          size_t saved_size, void* net_out, float* d, float* w,
+                                          void* stream) {
+  if (dim != kD || wdtype != DPVO_F32 || iodtype != DPVO_F32) return DPVO_ERR_UNSUPPORTED;
+  if (K0 < 1) return DPVO_ERR_INVALID;
+  if (E <= 0) return DPVO_OK;
+  if (!blob || !net || !inp || !corr || !ix || !jx || !workspace || !saved || !net_out || !d || !w)
+    return DPVO_ERR_INVALID;
+  if (workspace_size < ws_bytes(E) || saved_size < upd::saved_bytes(E, K0))
+    return DPVO_ERR_WORKSPACE;
+  const Ws ws = ws_carve(workspace, E);
+  const upd::Saved sv = upd::saved_carve(saved, E, K0);
+  const Blob B{(const char*)blob, k0pad(K0), 4};
+  hipStream_t st = as_stream(stream);
+  return E >= kUpdateBigTileE
+             ? forward_t<float, 2, true>(B, net, inp, corr, ix, jx, E, K0, 0, ws, &sv, net_out, d, w, st)
+             : forward_t<float, 1, true>(B, net, inp, corr, ix, jx, E, K0, 0, ws, &sv, net_out, d, w, st);
+}
+
+DPVO_EXPORT int dpvo_update_saved_relu_masks(const void* saved, size_t saved_size, int E, int K0,
+                                             uint8_t* masks, void* stream) {
+  if (K0 < 1) return DPVO_ERR_INVALID;
+  if (E <= 0) return DPVO_OK;
+  if (!saved || !masks) return DPVO_ERR_INVALID;
+  if (saved_size < upd::saved_bytes(E, K0)) return DPVO_ERR_WORKSPACE;
+  const upd::Saved sv = upd::saved_carve(const_cast<void*>(saved), E, K0);
+  const size_t n = (size_t)E * kD;
+  hipLaunchKernelGGL(k_relu_masks, dim3((unsigned)((n + 255) / 256), 6), dim3(256), 0,
+                     as_stream(stream), (const float*)sv.pl[0], rows_bytes(E) / 4, E, masks);
+  return launch_status();
 }

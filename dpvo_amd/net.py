@@ -3,7 +3,8 @@ on the MI355X.
 
 ``Update`` has the reference module's parameter names, so a DPVO checkpoint's
 ``update.*`` keys load unchanged, and the reference's call signature; the
-forward pass is the fused HIP operator of csrc/update_op.hip (inference only).
+forward pass is the fused HIP operator of csrc/update_op.hip, and with
+``differentiable=True`` its backward is csrc/update_bwd.hip.
 The parameters stay fp32 tensors; ``dtype`` chooses how they are packed for
 the matrix cores: ``torch.float16`` (fp16 operands, fp32 accumulation) or
 ``torch.float32`` (exact fp32 products).
@@ -46,20 +47,83 @@ def _mlp(i, o):
     return nn.Sequential(nn.Linear(i, o), nn.ReLU(inplace=True), nn.Linear(o, o))
 
 
+class _UpdateFunction(torch.autograd.Function):
+    """forward_train + backward of the update operator.  Inputs: the module, the
+    index tensors (ix, jx, gk, gij: int64 [E], no gradient), net, inp [E, 384],
+    corr [E, K0] (contiguous fp32) and the 50 parameters.  The blob is packed
+    on the device from the parameters' current values and ``saved`` is
+    allocated per call, so neither an optimiser step nor further forward calls
+    before the backward disturb it.  Once-differentiable; no host
+    synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, mod, ix, jx, gk, gij, net, inp, corr, *params):
+        x = ext()
+        dev = net.device
+        E, K0 = net.shape[0], mod.corr_dim
+        ps = [p.detach().contiguous() for p in params]
+        blob = torch.empty(x.packed_bytes(K0, x.F32), dtype=torch.uint8, device=dev)
+        x.pack_weights_device(ps, K0, x.F32, blob)
+        saved = torch.empty(x.saved_bytes(E, K0), dtype=torch.uint8, device=dev)
+        net_out = torch.empty(E, DIM, dtype=torch.float32, device=dev)
+        d = torch.empty(E, 2, dtype=torch.float32, device=dev)
+        w = torch.empty(E, 2, dtype=torch.float32, device=dev)
+        ws = mod.workspace(E, dev)
+        x.plan(gk, gij, ws)
+        x.forward_train(blob, net, inp, corr, ix, jx, ws, saved, net_out, d, w)
+        ctx.K0 = K0
+        ctx.saved = saved
+        ctx.set_materialize_grads(False)  # an unused output's cotangent stays None: no zeros
+        ctx.save_for_backward(ix, jx, *params)
+        return net_out, d, w
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_net_out, g_d, g_w):
+        x = ext()
+        ix, jx, *params = ctx.saved_tensors
+        E, K0, dev = ix.numel(), ctx.K0, ix.device
+        need = ctx.needs_input_grad  # mod, ix, jx, gk, gij, net, inp, corr, params...
+        cot = [None if g is None else g.to(torch.float32).contiguous()
+               for g in (g_net_out, g_d, g_w)]
+        out = [torch.empty(E, c, dtype=torch.float32, device=dev) if need[5 + i] else None
+               for i, c in enumerate((DIM, DIM, K0))]
+        ps = [p.detach().contiguous() for p in params]
+        want = any(need[8:])
+        grads = [torch.empty_like(p) for p in ps] if want else []
+        ws = torch.empty(x.backward_workspace_bytes(E, K0), dtype=torch.uint8, device=dev)
+        x.backward(ps, ctx.saved, ix, jx, K0, cot[0], cot[1], cot[2], out[0], out[1], out[2], grads,
+                   ws)
+        pg = tuple(g if n else None for g, n in zip(grads, need[8:])) if want \
+            else (None,) * len(params)
+        return (None,) * 5 + tuple(out) + pg
+
+
 class Update(nn.Module):
-    """Drop-in for ``dpvo.net.Update`` (inference).
+    """Drop-in for ``dpvo.net.Update``.
 
     forward(net, inp, corr, flow, ii, jj, kk, ix=None, jx=None, gk=None, gij=None)
     -> (net, (d, w, None)), shapes [1, E, .] as in the reference.  ix / jx
     default to ``fastba.neighbors(kk, jj)`` (-1 = missing, masked), gk to kk and
     gij to ``ii * 12345 + jj``: the original DPVO.  For the fork's live Update
     pass ``ix, jx = neighbors_tensor(kk, jj)`` and ``gij=ii``.
+
+    ``differentiable=False`` (default): inference, under ``no_grad``.
+    ``differentiable=True`` (``dtype`` must be ``torch.float32``): when grad
+    mode is on, net / inp / corr are fp32 and any of them or a parameter
+    requires grad, the outputs (the same bits as the inference path) carry
+    gradients to net, inp, corr and the 50 parameters, formed by the HIP
+    backward for exactly the inputs that need them.  The gradient of
+    ``agg_*.g.bias`` is analytically zero; what arrives is rounding noise.
     """
 
-    def __init__(self, p=3, dtype=torch.float16, corr_dim=None):
+    def __init__(self, p=3, dtype=torch.float16, corr_dim=None, differentiable=False):
         super().__init__()
         if dtype not in (torch.float16, torch.float32):
             raise ValueError("Update: dtype (the packed weight type) is float16 or float32")
+        if differentiable and dtype != torch.float32:
+            raise ValueError("Update: differentiable=True needs dtype=torch.float32")
+        self.differentiable = bool(differentiable)
         self.wdtype = dtype
         self.corr_dim = int(corr_dim) if corr_dim is not None else 2 * 49 * p * p
         self.c1 = _mlp(DIM, DIM)
@@ -114,8 +178,48 @@ class Update(nn.Module):
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
-    @torch.no_grad()
     def forward(self, net, inp, corr, flow, ii, jj, kk, ix=None, jx=None, gk=None, gij=None):
+        train = (self.differentiable and torch.is_grad_enabled()
+                 and all(t.dtype == torch.float32 for t in (net, inp, corr))
+                 and (any(t.requires_grad for t in (net, inp, corr))
+                      or any(p.requires_grad for p in self.parameters())))
+        if train:
+            return self._forward_train(net, inp, corr, ii, jj, kk, ix, jx, gk, gij)
+        with torch.no_grad():
+            return self._forward(net, inp, corr, ii, jj, kk, ix, jx, gk, gij)
+
+    def _indices(self, ii, jj, kk, ix, jx, gk, gij):
+        ii, jj, kk = (t.reshape(-1).long() for t in (ii, jj, kk))
+        if ix is None or jx is None:
+            from . import fastba
+
+            ix, jx = fastba.neighbors(kk, jj)
+        gk = kk if gk is None else gk
+        gij = ii * 12345 + jj if gij is None else gij
+        return tuple(t.reshape(-1).long().contiguous() for t in (ix, jx, gk, gij))
+
+    def _forward_train(self, net, inp, corr, ii, jj, kk, ix, jx, gk, gij):
+        require_gpu(net)
+        if net.dim() != 3 or net.shape[0] != 1 or net.shape[2] != DIM:
+            raise ValueError("Update: net must be [1, E, 384]")
+        E = net.shape[1]
+        if corr.shape[-1] != self.corr_dim:
+            raise ValueError(f"Update: corr has {corr.shape[-1]} features, the module "
+                             f"{self.corr_dim}")
+        if E == 0:
+            with torch.no_grad():
+                return self._forward(net, inp, corr, ii, jj, kk, ix, jx, gk, gij)
+        with torch.no_grad():
+            ix, jx, gk, gij = self._indices(ii, jj, kk, ix, jx, gk, gij)
+        params = list(self.parameters())
+        if len(params) != 50:
+            raise RuntimeError("Update: expected 50 parameter tensors")
+        net_out, d, w = _UpdateFunction.apply(
+            self, ix, jx, gk, gij, net.reshape(E, DIM).contiguous(),
+            inp.reshape(E, DIM).contiguous(), corr.reshape(E, self.corr_dim).contiguous(), *params)
+        return net_out.view(1, E, DIM), (d.view(1, E, 2), w.view(1, E, 2), None)
+
+    def _forward(self, net, inp, corr, ii, jj, kk, ix=None, jx=None, gk=None, gij=None):
         require_gpu(net)
         if net.dim() != 3 or net.shape[0] != 1 or net.shape[2] != DIM:
             raise ValueError("Update: net must be [1, E, 384]")
@@ -238,13 +342,13 @@ class VONet(nn.Module):
     """Container with ``dpvo.net.VONet``'s attribute names (net.py:426-434), so
     a DPVO checkpoint's ``patchify.*`` / ``update.*`` keys load unchanged.
     ``dtype`` is the packed weight type of both modules; ``differentiable``
-    goes to the patchifier's encoders (the update operator has no backward)."""
+    goes to the patchifier's encoders and to the update operator (fp32 only)."""
 
     def __init__(self, dtype=torch.float16, differentiable=False):
         super().__init__()
         self.P = 3
         self.patchify = Patchifier(self.P, dtype=dtype, differentiable=differentiable)
-        self.update = Update(p=self.P, dtype=dtype)
+        self.update = Update(p=self.P, dtype=dtype, differentiable=differentiable)
         self.DIM = DIM
         self.RES = 4
 

@@ -812,9 +812,10 @@ int dpvo_triangulate_tracks(const float* poses, const float* intrinsics, const f
 
 /* --------------------------------------------------------- update operator */
 
-/* DPVO's update operator, inference only (dpvo/net.py:175-339 `Update`, with
+/* DPVO's update operator (dpvo/net.py:175-339 `Update`, with
    blocks.py:15-29 GatedResidual and net.py:671-714 SoftAggONNX / blocks.py:31-48
-   SoftAgg), as fused kernels on the matrix cores.  dim must be 384.
+   SoftAgg), as fused kernels on the matrix cores: the inference forward, and
+   further down the training forward and the backward.  dim must be 384.
 
      t  = corr MLP(corr)                       net.py:201-208
      x  = LN(net + inp + t)                    net.py:283-284
@@ -880,6 +881,73 @@ int dpvo_update_forward(const void* blob, int wdtype, const void* net, const voi
                         const void* corr, const int64_t* ix, const int64_t* jx, int E, int dim,
                         int K0, int iodtype, void* workspace, size_t workspace_size,
                         void* net_out, float* d, float* w, void* stream);
+
+/* --- the update operator's training surface (csrc/update_op.hip,
+   csrc/update_bwd.hip) ---
+   fp32 weights and fp32 I/O only.  Exact fp32 products
+   (v_mfma_f32_16x16x4_f32); every sum over edges or over the members of a group
+   runs in a fixed order that depends on E and the indices only (fixed chunks
+   folded in fp64, ascending edge order inside a group), no float atomics: two
+   calls on the same state are bit-identical.  Plain launches on `stream`, no
+   allocation, no host synchronisation.  Status rules of all entry points, all
+   checked before any launch: dim != 384 or a dtype other than DPVO_F32 (the
+   device pack also takes DPVO_F16): DPVO_ERR_UNSUPPORTED; K0 < 1:
+   DPVO_ERR_INVALID; then E <= 0: DPVO_OK without a launch; null required
+   pointers: DPVO_ERR_INVALID; short buffers: DPVO_ERR_WORKSPACE. */
+
+/* DEVICE pack: the blob of dpvo_update_pack_weights, byte for byte (header and
+   zero padding included), written by one launch from `params`, a host array
+   of the 50 device fp32 tensors in state_dict order.  For the step after an
+   optimiser update: no host round trip.  wdtype DPVO_F32 or DPVO_F16. */
+int dpvo_update_pack_weights_device(const float* const* params, int dim, int K0, int wdtype,
+                                    void* blob, size_t blob_size, void* stream);
+
+/* Bytes of the `saved` buffer of dpvo_update_forward_train (layout:
+   csrc/update_layout.hpp; 25 fp32 planes [E, 384], corr, w and the two group
+   plans: 38456 + 4 K0 bytes per edge); 0 for E < 1 or K0 < 1. */
+size_t dpvo_update_saved_bytes(int E, int K0);
+
+/* dpvo_update_forward (after dpvo_update_plan on the same workspace) with
+   DPVO_F32 weights and I/O: the same nine launches with the same arithmetic,
+   so net_out, d and w are bit-identical to the inference call at every E, and
+   one more launch that copies the two group plans.  Everything the backward
+   needs is kept in the caller-owned `saved`; the workspace may be reused
+   (with another E, too) before the backward runs. */
+int dpvo_update_forward_train(const void* blob, int wdtype, const void* net, const void* inp,
+                              const void* corr, const int64_t* ix, const int64_t* jx, int E,
+                              int dim, int K0, int iodtype, void* workspace,
+                              size_t workspace_size, void* saved, size_t saved_size,
+                              void* net_out, float* d, float* w, void* stream);
+
+/* One launch: the six ReLU masks the training forward used, uint8
+   [6, E, 384] (1 where the ReLU passed), in the order corr.0, the ReLU after
+   corr.3, c1.0, c2.0, gru.1.res.0, gru.3.res.0.  The seventh, the heads'
+   relu(x), is net_out > 0. */
+int dpvo_update_saved_relu_masks(const void* saved, size_t saved_size, int E, int K0,
+                                 uint8_t* masks, void* stream);
+
+/* Bytes of the backward's device workspace; 0 for E < 1 or K0 < 1. */
+size_t dpvo_update_backward_workspace_bytes(int E, int K0);
+
+/* The backward.  params: host array of the 50 device fp32 parameter tensors
+   (PyTorch layout, state_dict order; the values the forward's blob was packed
+   from).  saved: as filled by dpvo_update_forward_train with the same (E, K0);
+   ix, jx: as given to it.  Cotangents g_net_out [E, 384], g_d, g_w [E, 2]:
+   each may be null, which means zero (bit-identical to a buffer of zeros).
+   Outputs g_net, g_inp [E, 384], g_corr [E, K0]: each may be null (not wanted,
+   not computed; the other outputs' bits do not change).  grads: host array of
+   50 device fp32 tensors shaped like params, every element overwritten; or
+   null when no parameter gradient is wanted.  agg_kk.g.bias and
+   agg_ij.g.bias have an analytically zero gradient (the group softmax is
+   shift-invariant per channel): what is written is what the arithmetic
+   gives, rounding noise.  A null entry of params or grads: DPVO_ERR_INVALID;
+   E above 65535 * 64: DPVO_ERR_UNSUPPORTED.  3 + 141 launches with every
+   gradient wanted. */
+int dpvo_update_backward(const float* const* params, int dim, int K0, const void* saved,
+                         size_t saved_size, const int64_t* ix, const int64_t* jx, int E,
+                         const float* g_net_out, const float* g_d, const float* g_w, float* g_net,
+                         float* g_inp, float* g_corr, float* const* grads, void* workspace,
+                         size_t workspace_size, void* stream);
 
 /* ---------------------------------------------------------------------------
    The feature encoders (replace BasicEncoder4, dpvo/extractor.py:200-264: the
