@@ -11,6 +11,8 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
   (dpvo.py __call__ head, terminate / get_pose)      -> dpvo_amd.frontend
   (dpvo.py DPVO, config.py, net.py VONet)            -> dpvo_amd.DPVO,
                      the tracker class                   default_config, VONet
+  (net.py VONet.forward, train.py loss and step)      -> dpvo_amd.VONet.forward,
+                     the training step                   dpvo_amd.training
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -20,7 +22,8 @@ from ._native import EXT_NAMES, NATIVE_DIR, c_abi, load_extension  # noqa: F401
 __version__ = "0.1.0"
 
 __all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "frontend", "load_extension",
-           "c_abi", "BasicEncoder4", "Patchifier", "tracker", "DPVO", "default_config", "VONet"]
+           "c_abi", "BasicEncoder4", "Patchifier", "tracker", "DPVO", "default_config", "VONet", "training",
+           "CorrBlock", "training_schedule", "flow_loss", "pose_loss", "sequence_loss", "train_step"]
 
 
 def __getattr__(name):  # the classes, without importing torch.nn at package import
@@ -28,10 +31,14 @@ def __getattr__(name):  # the classes, without importing torch.nn at package imp
         from . import dpvo
 
         return getattr(dpvo, name)
-    if name == "VONet":
-        from .net import VONet
+    if name in ("VONet", "CorrBlock", "training_schedule"):
+        from . import net
 
-        return VONet
+        return getattr(net, name)
+    if name in ("flow_loss", "pose_loss", "sequence_loss", "train_step"):
+        from . import training
+
+        return getattr(training, name)
     if name == "BasicEncoder4":
         from .extractor import BasicEncoder4
 

@@ -34,7 +34,7 @@ ARCH = os.environ.get("DPVO_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["corr.hip", "corr_nhwc.hip", "corr_nchw.hip", "ba.hip", "ba_window.hip", "ba_large.hip", "lie.hip", "pgo.hip", "pg.hip",
                "keyframe.hip", "spd_solve.hip", "ransac.hip", "update_op.hip", "update_bwd.hip", "encoder.hip", "encoder_bwd.hip",
-               "frontend.hip", "ba_layer.hip", "tracker.hip", "match.hip", "triangulate.hip"]
+               "frontend.hip", "ba_layer.hip", "tracker.hip", "match.hip", "triangulate.hip", "train.hip"]
 EXTENSIONS = {
     "cuda_corr": "ext_cuda_corr.cpp",
     "cuda_ba": "ext_cuda_ba.cpp",

@@ -1203,6 +1203,174 @@ std::vector<torch::Tensor> ba_layer_backward(torch::Tensor ws, torch::Tensor pos
   return {gT, gW, gP, gK};
 }
 
+// The training step's reprojection and losses (train.hip): fp32 tensors, no
+// host synchronisation in any call.
+static torch::Tensor f32c(torch::Tensor t, const char* name) {
+  check_device(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "cuda_ba: ", name, " must be float32");
+  return t.contiguous();
+}
+
+struct TransformIn {
+  int E, M, P, N;
+};
+
+static TransformIn transform_inputs(torch::Tensor& poses, torch::Tensor& patches,
+                                    torch::Tensor& intrinsics, torch::Tensor& ii,
+                                    torch::Tensor& jj, torch::Tensor& kk) {
+  poses = f32c(poses, "poses");
+  patches = f32c(patches, "patches");
+  intrinsics = f32c(intrinsics, "intrinsics");
+  TORCH_CHECK(poses.dim() >= 2 && poses.size(-1) == 7, "poses must be [.., N, 7]");
+  TORCH_CHECK(patches.dim() >= 4 && patches.size(-3) == 3 && patches.size(-1) == patches.size(-2),
+              "patches must be [.., M, 3, P, P]");
+  ii = idx64(ii, "ii");
+  jj = idx64(jj, "jj");
+  kk = idx64(kk, "kk");
+  TransformIn t;
+  t.E = ii.numel();
+  TORCH_CHECK(jj.numel() == t.E && kk.numel() == t.E, "ii, jj, kk must have equal length");
+  t.P = patches.size(-1);
+  t.N = poses.numel() / 7;
+  t.M = patches.numel() / (3 * (int64_t)t.P * t.P);
+  TORCH_CHECK(intrinsics.numel() == 4 * (int64_t)t.N, "intrinsics must be [.., N, 4]");
+  return t;
+}
+
+// -> [coords [E, P, P, 2], valid [E, P, P]] (+ coords_corr [E, 2, P, P])
+std::vector<torch::Tensor> transform_forward(torch::Tensor poses, torch::Tensor patches,
+                                             torch::Tensor intrinsics, torch::Tensor ii,
+                                             torch::Tensor jj, torch::Tensor kk, bool with_corr) {
+  const TransformIn t = transform_inputs(poses, patches, intrinsics, ii, jj, kk);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  auto coords = torch::empty({t.E, t.P, t.P, 2}, poses.options());
+  auto valid = torch::empty({t.E, t.P, t.P}, poses.options());
+  torch::Tensor corr;
+  if (with_corr) corr = torch::empty({t.E, 2, t.P, t.P}, poses.options());
+  check_status(dpvo_transform_forward(poses.data_ptr<float>(), patches.data_ptr<float>(),
+                                      intrinsics.data_ptr<float>(), ii.data_ptr<int64_t>(),
+                                      jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), t.E, t.P, t.N,
+                                      t.M, coords.data_ptr<float>(), valid.data_ptr<float>(),
+                                      with_corr ? corr.data_ptr<float>() : nullptr,
+                                      current_stream()),
+               "cuda_ba.transform_forward");
+  if (with_corr) return {coords, valid, corr};
+  return {coords, valid};
+}
+
+// -> [g_poses [N, 6] or undefined, g_patches [M, 3, P, P] or undefined]
+std::vector<c10::optional<torch::Tensor>> transform_backward(
+    torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics, torch::Tensor ii,
+    torch::Tensor jj, torch::Tensor kk, torch::Tensor g_coords, bool want_poses,
+    bool want_patches) {
+  const TransformIn t = transform_inputs(poses, patches, intrinsics, ii, jj, kk);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  g_coords = f32c(g_coords, "g_coords");
+  TORCH_CHECK(g_coords.numel() == 2 * (int64_t)t.E * t.P * t.P, "g_coords must be [E, P, P, 2]");
+  const auto mk = [&](std::vector<int64_t> s) {  // every row is written by the kernels
+    return t.E == 0 ? torch::zeros(s, poses.options()) : torch::empty(s, poses.options());
+  };
+  c10::optional<torch::Tensor> gP, gK;
+  if (want_poses) gP = mk({t.N, 6});
+  if (want_patches) gK = mk({t.M, 3, t.P, t.P});
+  const size_t wsb = dpvo_transform_workspace_bytes(t.E, t.P);
+  auto ws = torch::empty({(int64_t)std::max<size_t>(wsb, 8)}, poses.options().dtype(torch::kUInt8));
+  check_status(dpvo_transform_backward(poses.data_ptr<float>(), patches.data_ptr<float>(),
+                                       intrinsics.data_ptr<float>(), ii.data_ptr<int64_t>(),
+                                       jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), t.E, t.P,
+                                       t.N, t.M, g_coords.data_ptr<float>(),
+                                       gP ? gP->data_ptr<float>() : nullptr,
+                                       gK ? gK->data_ptr<float>() : nullptr, ws.data_ptr(), wsb,
+                                       current_stream()),
+               "cuda_ba.transform_backward");
+  return {gP, gK};
+}
+
+// -> [loss [1], count [1] int32, emin [E], argmin [E] int32]
+std::vector<torch::Tensor> flow_loss_forward(torch::Tensor coords, torch::Tensor coords_gt,
+                                             torch::Tensor valid) {
+  coords = f32c(coords, "coords");
+  coords_gt = f32c(coords_gt, "coords_gt");
+  valid = f32c(valid, "valid");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(coords.device());
+  TORCH_CHECK(coords.dim() >= 4 && coords.size(-1) == 2 && coords.size(-2) == coords.size(-3),
+              "coords must be [.., E, P, P, 2]");
+  const int P = coords.size(-2);
+  const int64_t E = coords.numel() / (2 * (int64_t)P * P);
+  TORCH_CHECK(coords_gt.numel() == coords.numel() && valid.numel() == E,
+              "coords_gt must match coords and valid must be [E]");
+  const auto i32 = coords.options().dtype(torch::kInt32);
+  auto loss = torch::zeros({1}, coords.options());
+  auto count = torch::zeros({1}, i32);
+  auto emin = torch::empty({E}, coords.options());
+  auto amin = torch::empty({E}, i32);
+  check_status(dpvo_flow_loss_forward(coords.data_ptr<float>(), coords_gt.data_ptr<float>(),
+                                      valid.data_ptr<float>(), (int)E, P, loss.data_ptr<float>(),
+                                      count.data_ptr<int32_t>(), emin.data_ptr<float>(),
+                                      amin.data_ptr<int32_t>(), current_stream()),
+               "cuda_ba.flow_loss_forward");
+  return {loss, count, emin, amin};
+}
+
+torch::Tensor flow_loss_backward(torch::Tensor coords, torch::Tensor coords_gt, torch::Tensor valid,
+                                 torch::Tensor count, torch::Tensor argmin, torch::Tensor g_loss) {
+  coords = f32c(coords, "coords");
+  coords_gt = f32c(coords_gt, "coords_gt");
+  valid = f32c(valid, "valid");
+  g_loss = f32c(g_loss, "g_loss");
+  check_device(count, "count");
+  check_device(argmin, "argmin");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(coords.device());
+  const int P = coords.size(-2);
+  const int64_t E = coords.numel() / (2 * (int64_t)P * P);
+  TORCH_CHECK(count.scalar_type() == torch::kInt32 && argmin.scalar_type() == torch::kInt32 &&
+                  count.numel() == 1 && argmin.numel() == E && g_loss.numel() == 1 &&
+                  valid.numel() == E && coords_gt.numel() == coords.numel(),
+              "cuda_ba.flow_loss_backward: buffers of another forward call");
+  auto g = torch::empty_like(coords);
+  check_status(dpvo_flow_loss_backward(coords.data_ptr<float>(), coords_gt.data_ptr<float>(),
+                                       valid.data_ptr<float>(), count.data_ptr<int32_t>(),
+                                       argmin.contiguous().data_ptr<int32_t>(),
+                                       g_loss.data_ptr<float>(), (int)E, P, g.data_ptr<float>(),
+                                       current_stream()),
+               "cuda_ba.flow_loss_backward");
+  return g;
+}
+
+// -> [out [3] = (mean tr, mean ro, s), tr [n (n - 1)], ro [n (n - 1)]]
+std::vector<torch::Tensor> pose_loss_forward(torch::Tensor G, torch::Tensor Ps) {
+  G = f32c(G, "G");
+  Ps = f32c(Ps, "Ps");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(G.device());
+  TORCH_CHECK(G.dim() >= 2 && G.size(-1) == 7 && Ps.numel() == G.numel(),
+              "G and Ps must be [.., n, 7]");
+  const int64_t n = G.numel() / 7;
+  const int64_t np = n > 1 ? n * (n - 1) : 0;
+  auto out = torch::zeros({3}, G.options());  // n < 2: zeros, nothing launched
+  auto tr = torch::empty({np}, G.options()), ro = torch::empty({np}, G.options());
+  check_status(dpvo_pose_loss_forward(G.data_ptr<float>(), Ps.data_ptr<float>(), (int)n,
+                                      out.data_ptr<float>(), tr.data_ptr<float>(),
+                                      ro.data_ptr<float>(), current_stream()),
+               "cuda_ba.pose_loss_forward");
+  return {out, tr, ro};
+}
+
+torch::Tensor pose_loss_backward(torch::Tensor G, torch::Tensor Ps, torch::Tensor g_out) {
+  G = f32c(G, "G");
+  Ps = f32c(Ps, "Ps");
+  g_out = f32c(g_out, "g_out");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(G.device());
+  TORCH_CHECK(G.size(-1) == 7 && Ps.numel() == G.numel() && g_out.numel() == 2,
+              "G and Ps must be [.., n, 7], g_out [2]");
+  const int64_t n = G.numel() / 7;
+  auto gG = n < 2 ? torch::zeros({n, 6}, G.options()) : torch::empty({n, 6}, G.options());
+  check_status(dpvo_pose_loss_backward(G.data_ptr<float>(), Ps.data_ptr<float>(), (int)n,
+                                       g_out.data_ptr<float>(), gG.data_ptr<float>(),
+                                       current_stream()),
+               "cuda_ba.pose_loss_backward");
+  return gG;
+}
+
 // PatchGraph.edges_loop (patchgraph.py:65-91) gated as dpvo.py:984-988
 void edges_loop(torch::Tensor poses, torch::Tensor patches, torch::Tensor intrinsics,
                 torch::Tensor ix, int64_t M, torch::Tensor st, int64_t n_cap,
@@ -1676,6 +1844,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "lmbda tensor or None, lmbda float, ii, jj, kk, n, fixedp, structure_only, bounds, ep, "
         "with_backward) -> [dX [n_free, 6], dZ [M], workspace (int32 words: out-of-range edges, "
         "factorisation info)]");
+  m.def("transform_forward", &transform_forward,
+        "projective_ops.transform, one launch: (poses, patches, intrinsics, ii, jj, kk, with_corr) "
+        "-> [coords [E,P,P,2], valid [E,P,P] (, coords [E,2,P,P])]");
+  m.def("transform_backward", &transform_backward,
+        "adjoint of transform_forward: (.., g_coords, want_poses, want_patches) -> "
+        "[g_poses [N,6] | None, g_patches [M,3,P,P] | None]");
+  m.def("flow_loss_forward", &flow_loss_forward,
+        "train.py:87-88: (coords, coords_gt, valid [E]) -> [loss, count, emin, argmin]");
+  m.def("flow_loss_backward", &flow_loss_backward,
+        "(coords, coords_gt, valid, count, argmin, g_loss) -> g_coords");
+  m.def("pose_loss_forward", &pose_loss_forward,
+        "train.py:90-113: (G, Ps [n,7]) -> [(mean tr, mean ro, s), tr, ro]");
+  m.def("pose_loss_backward", &pose_loss_backward, "(G, Ps, g_out [2]) -> g_G [n,6]");
   m.def("ba_layer_backward", &ba_layer_backward,
         "adjoint of ba_layer_forward on its workspace: (ws, poses, patches, intrinsics, ii, jj, kk, "
         "gX, gZ, n, fixedp, structure_only) -> [g_targets, g_weights, g_poses [N, 6], g_patches [M, 3]]");

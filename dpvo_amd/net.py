@@ -1,5 +1,5 @@
-"""DPVO's update operator (dpvo/net.py:175-339) and patchifier (net.py:344-407)
-on the MI355X.
+"""DPVO's update operator (dpvo/net.py:175-339), patchifier (net.py:344-407),
+CorrBlock (410-423) and VONet with its training unroll (426-522) on the MI355X.
 
 ``Update`` has the reference module's parameter names, so a DPVO checkpoint's
 ``update.*`` keys load unchanged, and the reference's call signature; the
@@ -338,11 +338,91 @@ class Patchifier(nn.Module):
         return fmap, gmap, imap, patches, index
 
 
+class CorrBlock:
+    """``dpvo.net.CorrBlock`` (net.py:410-423): the correlation of every edge's
+    gmap patch against an ``avg_pool2d`` pyramid of fmap, through
+    ``altcorr.corr`` (A-CORR and A-CORR-BWD).  ``dropout`` is the fraction of
+    edges whose gradient the backward keeps (correlation.py:31-36; 1 keeps all,
+    no random draw)."""
+
+    def __init__(self, fmap, gmap, radius=3, dropout=0.2, levels=(1, 4)):
+        self.dropout = dropout
+        self.radius = radius
+        self.levels = tuple(levels)
+        self.gmap = gmap
+        b, n, c, h, w = fmap.shape
+        self.pyramid = [torch.nn.functional.avg_pool2d(fmap.view(b * n, c, h, w), l, stride=l)
+                        .view(b, n, c, h // l, w // l) for l in self.levels]
+
+    def __call__(self, ii, jj, coords):
+        from . import altcorr
+
+        corrs = [altcorr.corr(self.gmap, self.pyramid[i], coords / self.levels[i], ii, jj,
+                              self.radius, self.dropout) for i in range(len(self.levels))]
+        return torch.stack(corrs, -1).view(1, len(ii), -1)
+
+
+def _schedule(n_frames, patches_per_image, steps, init_frames=8, drop=None):
+    """The steps of net.py:458-497 on the host, as dicts of numpy int64 arrays:
+    ii / jj / kk / n, ``new`` (edges prepended at this step), ``keep`` (indices
+    kept by the 10 % removal, or None) and ``loss`` (indices of the edges with
+    0 < |ii - jj| <= 2)."""
+    import numpy as np
+
+    if n_frames < init_frames or init_frames < 2 or patches_per_image < 1:
+        # a new frame's depth is the median of the two frames before it
+        raise ValueError("training_schedule: need 2 <= init_frames <= n_frames, "
+                         "patches_per_image >= 1")
+    if drop is None:
+        def drop(step):
+            return np.random.rand() < 0.1
+    ix = np.arange(n_frames * patches_per_image, dtype=np.int64) // patches_per_image
+
+    def mesh(a, b):  # flatmeshgrid(a, b, indexing='ij')
+        return np.repeat(a, len(b)), np.tile(b, len(a))
+
+    kk, jj = mesh(np.nonzero(ix < init_frames)[0], np.arange(0, init_frames, dtype=np.int64))
+    ii = ix[kk]
+    out = []
+    while len(out) < steps:
+        n = int(ii.max()) + 1
+        new, keep = 0, None
+        if len(out) >= init_frames and n < n_frames:
+            kk1, jj1 = mesh(np.nonzero(ix < n)[0], np.arange(n, n + 1, dtype=np.int64))
+            kk2, jj2 = mesh(np.nonzero(ix == n)[0], np.arange(0, n + 1, dtype=np.int64))
+            ii = np.concatenate([ix[kk1], ix[kk2], ii])
+            jj = np.concatenate([jj1, jj2, jj])
+            kk = np.concatenate([kk1, kk2, kk])
+            new = len(kk1) + len(kk2)
+            if drop(len(out)):
+                keep = np.nonzero((ii != n - 4) & (jj != n - 4))[0]
+                ii, jj, kk = ii[keep], jj[keep], kk[keep]
+            n = int(ii.max()) + 1
+        dij = np.abs(ii - jj)
+        out.append({"ii": ii, "jj": jj, "kk": kk, "n": n, "new": new, "keep": keep,
+                    "loss": np.nonzero((dij > 0) & (dij <= 2))[0]})
+    return out
+
+
+def training_schedule(n_frames, patches_per_image, steps, init_frames=8, drop=None):
+    """The edge lists ``(ii, jj, kk, n)`` of every unrolled step of
+    ``VONet.forward`` (net.py:458-497), built on the host: patch k lies in frame
+    ``k // patches_per_image``, so nothing is read from the device.  The graph
+    starts on ``init_frames`` (at least 2) frames; from step ``init_frames`` on, each step
+    adds one frame until ``n_frames`` are in, its edges prepended in the
+    reference's order of ``cat``s.  ``drop`` (``step -> bool``; default: a host
+    RNG draw < 0.1 per growth step) decides the removal of every edge that
+    touches frame ``n - 4``.  ii / jj / kk are int64 CPU tensors, n an int."""
+    return [(torch.from_numpy(s["ii"]), torch.from_numpy(s["jj"]), torch.from_numpy(s["kk"]), s["n"])
+            for s in _schedule(n_frames, patches_per_image, steps, init_frames, drop)]
+
+
 class VONet(nn.Module):
-    """Container with ``dpvo.net.VONet``'s attribute names (net.py:426-434), so
-    a DPVO checkpoint's ``patchify.*`` / ``update.*`` keys load unchanged.
-    ``dtype`` is the packed weight type of both modules; ``differentiable``
-    goes to the patchifier's encoders and to the update operator (fp32 only)."""
+    """``dpvo.net.VONet`` (net.py:426-522) with the reference's attribute
+    names, so a DPVO checkpoint's ``patchify.*`` / ``update.*`` keys load
+    unchanged.  ``dtype`` is the packed weight type of both modules;
+    ``differentiable`` goes to the patchifier's encoders and to the update
+    operator (fp32 only) and decides whether ``forward`` builds a graph."""
 
     def __init__(self, dtype=torch.float16, differentiable=False):
         super().__init__()
@@ -351,6 +431,134 @@ class VONet(nn.Module):
         self.update = Update(p=self.P, dtype=dtype, differentiable=differentiable)
         self.DIM = DIM
         self.RES = 4
+        self.differentiable = bool(differentiable)
+        self.wdtype = dtype
+
+    def forward(self, images, poses, disps, intrinsics, M=1024, STEPS=12, P=1,
+                structure_only=False, rescale=False, *, patches_per_image=80, init_frames=8,
+                coords=None, init_disps=None, edge_drop=0.1, corr_dropout=0.2):
+        """The training unroll of net.py:438-522, line for line: images
+        [1, N, 3, H, W] in 0..255, poses the ground-truth SE3 [1, N, 7], disps
+        [1, N, H, W], intrinsics [1, N, 4] at full resolution -> the list of
+        STEPS tuples ``(valid, coords, coords_gt, Gs[:, :n], Ps[:, :n], kl)``.
+        M, P and rescale are accepted and unused, as in the reference.
+
+        With ``differentiable=True, dtype=torch.float32`` (and grad mode on)
+        the trajectory carries gradients to every parameter tensor (22 per
+        encoder, 50 of the update operator): Gs and
+        patches are detached at the head of every step, the hidden state
+        ``net`` is not.  Otherwise the same values come out under ``no_grad``.
+        Batch size 1.  Autocast is off.  All three reprojections per step are
+        ``projective_ops.transform_fused``; the edge lists come from
+        ``training_schedule`` in one host-to-device copy; ``kl`` is a 0-d
+        device zero.
+
+        This build's additions (keyword-only): ``patches_per_image`` (the
+        reference's default 80) and ``init_frames`` (the reference's 8);
+        ``coords`` [N, patches_per_image, 2], the patch centres instead of the
+        random draw; ``init_disps`` [1, N * patches_per_image], the initial
+        patch depths instead of ``rand``; ``edge_drop``, the probability of
+        the removal of frame n - 4's edges at a growth step (0 never, 1
+        always); ``corr_dropout``, ``CorrBlock``'s."""
+        grad = (self.differentiable and self.wdtype == torch.float32 and torch.is_grad_enabled())
+        with torch.autocast("cuda", enabled=False), torch.set_grad_enabled(grad):
+            return self._unroll(images, poses, disps, intrinsics, STEPS, structure_only,
+                                patches_per_image, init_frames, coords, init_disps, edge_drop,
+                                corr_dropout)
+
+    def _unroll(self, images, poses, disps, intrinsics, STEPS, structure_only, ppi, init_frames,
+                centres, init_disps, edge_drop, corr_dropout):
+        import numpy as np
+
+        from . import projective_ops as pops
+        from .ba import BA
+        from .lietorch import SE3
+
+        require_gpu(images)
+        if images.dim() != 5 or images.shape[0] != 1:
+            raise ValueError("VONet.forward: batch size 1 (images [1, N, 3, H, W])")
+        dev = images.device
+        images = 2 * (images / 255.0) - 0.5
+        intrinsics = intrinsics / 4.0
+        disps = disps[:, :, 1::4, 1::4].float()
+        if centres is not None:
+            ppi = centres.shape[1]
+
+        fmap, gmap, imap, patches, ix = self.patchify(images, patches_per_image=ppi, disps=disps,
+                                                      coords=centres)
+        corr_fn = CorrBlock(fmap, gmap, dropout=corr_dropout)
+        b, N, c, h, w = fmap.shape
+        p = self.P
+
+        patches_gt = patches.clone()
+        Ps = poses if isinstance(poses, SE3) else SE3(poses)
+        d = patches[..., 2, p // 2, p // 2]
+        depth = torch.rand_like(d) if init_disps is None else init_disps.to(dev, d.dtype).view(d.shape)
+        patches = patches.clone()
+        patches[..., 2, :, :] = depth[..., None, None]
+
+        # every step's edge lists, the loss edges and the kept edges of a
+        # removal: one pinned buffer, one asynchronous copy
+        sched = _schedule(N, ppi, STEPS, init_frames,
+                          lambda step: np.random.rand() < edge_drop)
+        parts, spans = [], []
+        for s in sched:
+            arrs = [s["ii"], s["jj"], s["kk"], s["loss"]] + ([] if s["keep"] is None else [s["keep"]])
+            spans.append([a.size for a in arrs])
+            parts += arrs
+        host = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.int64))
+        flat = host.pin_memory().to(dev, non_blocking=True)
+
+        imap = imap.view(b, -1, DIM)
+        net = torch.zeros(b, sched[0]["ii"].size if sched else 0, DIM, device=dev,
+                          dtype=torch.float32)
+        gdata = torch.zeros(1, N, 7, device=dev, dtype=torch.float32)  # SE3.IdentityLike(poses)
+        gdata[..., 6] = 1.0
+        Gs = SE3(Ps.data.detach().to(torch.float32).clone()) if structure_only else SE3(gdata)
+        kl = torch.zeros((), device=dev)
+
+        traj = []
+        bounds = [-64, -64, w + 64, h + 64]
+        at = 0
+        for s, span in zip(sched, spans):
+            idx = []
+            for m in span:
+                idx.append(flat[at:at + m])
+                at += m
+            ii, jj, kk, lk = idx[:4]
+            n = s["n"]
+            Gs = Gs.detach()
+            patches = patches.detach()
+            if s["new"]:
+                f = n - 1  # the frame that joins the graph at this step
+                if not structure_only:
+                    Gs = SE3(Gs.data.clone())
+                    Gs.data[:, f] = Gs.data[:, f - 1]
+                net = torch.cat([torch.zeros(b, s["new"], DIM, device=dev), net], dim=1)
+                if s["keep"] is not None:
+                    net = net[:, idx[4]]
+                patches = patches.clone()  # the median of the two frames before: a contiguous slice
+                patches[:, f * ppi:(f + 1) * ppi, 2] = torch.median(
+                    patches[:, (f - 2) * ppi:f * ppi, 2])
+
+            coords, coords1 = pops.transform_fused(Gs, patches, intrinsics, ii, jj, kk,
+                                                   corr_layout=True)
+            corr = corr_fn(kk, jj, coords1)
+            net, (delta, weight, _) = self.update(net, imap[:, kk], corr, None, ii, jj, kk)
+
+            lmbda = 1e-4
+            target = coords[..., p // 2, p // 2, :] + delta
+            ep = 10
+            for itr in range(2):
+                Gs, patches = BA(Gs, patches, intrinsics, target, weight, lmbda, ii, jj, kk, bounds,
+                                 ep=ep, fixedp=1, structure_only=structure_only, num_poses=n)
+
+            il, jl, kl_ = ii[lk], jj[lk], kk[lk]  # 0 < |ii - jj| <= 2
+            coords = pops.transform_fused(Gs, patches, intrinsics, il, jl, kl_)
+            coords_gt, valid = pops.transform_fused(Ps, patches_gt, intrinsics, il, jl, kl_,
+                                                    valid=True)
+            traj.append((valid[..., p // 2, p // 2], coords, coords_gt, Gs[:, :n], Ps[:, :n], kl))
+        return traj
 
     def load_checkpoint(self, path_or_state_dict):
         """Load a DPVO checkpoint (a path for ``torch.load`` or a state dict):

@@ -4,7 +4,9 @@ Restates dpvo/projective_ops.py (cuteboyqq/DPVO): iproj 19-29, proj 32-50,
 transform 53-113, point_cloud 115-117, flow_mag 120-130, so that DPVO's
 caller code (DPVO.reproject, ba.py) runs unchanged on the HIP lietorch ops.
 `reproject` is the fused single-kernel form used by the MI355X update loop
-(cuda_ba.reproject semantics: intrinsics row 0, no depth clamp).
+(cuda_ba.reproject semantics: intrinsics row 0, no depth clamp);
+`transform_fused` is `transform` itself (per-frame intrinsics, depth clamp,
+gradients) as one HIP launch each way, for the training unroll.
 """
 from __future__ import annotations
 
@@ -82,6 +84,64 @@ def transform(poses, patches, intrinsics, ii, jj, kk, depth=False, valid=False, 
     if valid:
         return x1, (X1[..., 2] > 0.2).float()
     return x1
+
+
+class _TransformFused(torch.autograd.Function):
+    """(pose data [1, N, 7], patches [1, M, 3, P, P]) -> (coords [E, P, P, 2],
+    valid [E, P, P], coords [E, 2, P, P] or an empty tensor): the forward and
+    backward of train.hip.  The pose gradient is a left-tangent row padded to
+    the embedding size, lietorch's convention; gradients are formed only for
+    the inputs that need them.  Once-differentiable, no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, pdata, patches, intrinsics, ii, jj, kk, with_corr):
+        out = cuda_ba.transform_forward(pdata, patches, intrinsics, ii, jj, kk, bool(with_corr))
+        coords, valid = out[0], out[1]
+        corr = out[2] if with_corr else coords.new_empty(0)
+        ctx.save_for_backward(pdata, patches, intrinsics, ii, jj, kk)
+        ctx.mark_non_differentiable(valid, corr)
+        return coords, valid, corr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_coords, _g_valid, _g_corr):
+        pdata, patches, intrinsics, ii, jj, kk = ctx.saved_tensors
+        want_pose, want_patch = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_coords is None or not (want_pose or want_patch):
+            return (None,) * 7
+        gP, gK = cuda_ba.transform_backward(pdata, patches, intrinsics, ii, jj, kk,
+                                            g_coords.to(torch.float32).contiguous(), want_pose,
+                                            want_patch)
+        if gP is not None:
+            gP = torch.nn.functional.pad(gP, (0, 1)).view(pdata.shape)
+        if gK is not None:
+            gK = gK.view(patches.shape)
+        return (gP, gK) + (None,) * 5
+
+
+def transform_fused(poses, patches, intrinsics, ii, jj, kk, valid=False, corr_layout=False):
+    """``transform(poses, patches, intrinsics, ii, jj, kk[, valid=True])`` for
+    SE3 and P in (1, 3) as one HIP launch each way (fp32 in and out, fp64
+    inside): coords [1, E, P, P, 2], with ``valid=True`` also (Z > 0.2) as
+    float [1, E, P, P], with ``corr_layout=True`` also the [1, E, 2, P, P] copy
+    A-CORR takes, written by the same launch (no gradient).  Gradients reach
+    ``poses`` (a left-tangent row padded to the embedding size) and
+    ``patches``, each in a fixed summation order; intrinsics get none.  Batch
+    size 1.  An edge with an index outside [0, N) / [0, M) gets NaN coords,
+    valid = 0 and no gradient instead of being read."""
+    pdata = poses.data if isinstance(poses, SE3) else poses
+    if isinstance(poses, Sim3):
+        raise ValueError("transform_fused: SE3 poses only")
+    if pdata.dim() != 3 or pdata.shape[0] != 1 or patches.dim() != 5 or patches.shape[0] != 1:
+        raise ValueError("transform_fused: batch size 1 (poses [1, N, 7], patches [1, M, 3, P, P])")
+    ii, jj, kk = (t.reshape(-1) for t in (ii, jj, kk))
+    coords, v, corr = _TransformFused.apply(pdata, patches, intrinsics, ii, jj, kk, corr_layout)
+    out = (coords[None],)
+    if valid:
+        out += (v[None],)
+    if corr_layout:
+        out += (corr[None],)
+    return out if len(out) > 1 else out[0]
 
 
 def point_cloud(poses, patches, intrinsics, ix):

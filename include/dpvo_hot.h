@@ -1065,6 +1065,74 @@ int dpvo_encoder_backward(int norm, int out_dim, const float* const* params, con
                           int grad_layout, float* const* grads, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+   The training step's reprojection and losses (csrc/train.hip).  fp32 in and
+   out, fp64 arithmetic and fixed-order fp64 sums inside, no floating-point
+   atomics (two calls give identical bits), plain launches on `stream`, no
+   allocation, no host synchronisation.  Status rules of all seven entries,
+   decided before any launch, in this order: an unsupported shape (P other
+   than 1 or 3, E P P >= 2^30, n > 32): DPVO_ERR_UNSUPPORTED; nothing to do
+   (E <= 0, n < 2, no gradient wanted): DPVO_OK without a launch; a null
+   required pointer (or N, M < 1): DPVO_ERR_INVALID; a short workspace:
+   DPVO_ERR_WORKSPACE. */
+
+/* projective_ops.transform (projective_ops.py:53-113) for SE3 and the whole
+   P x P patch.  poses [N, 7] (quaternions normalised on load), patches
+   [M, 3, P, P], intrinsics [N, 4] (row ii lifts, row jj projects), ii / jj /
+   kk [E] int64.  X1 = (G_j G_i^-1) ((x - cx) / fx, (y - cy) / fy, 1, d),
+   d' = 1 / max(Z, 0.1), coords [E, P, P, 2] = (fx d' X + cx, fy d' Y + cy),
+   valid [E, P, P] = Z > 0.2 as float; coords_corr (may be null): the same
+   coords as [E, 2, P, P], the layout A-CORR takes.  An edge with ii / jj
+   outside [0, N) or kk outside [0, M) reads nothing, gets NaN coords and
+   valid = 0, and contributes no gradient.  One launch. */
+int dpvo_transform_forward(const float* poses, const float* patches, const float* intrinsics,
+                           const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int P,
+                           int N, int M, float* coords, float* valid, float* coords_corr,
+                           void* stream);
+
+/* E (12 + 3 P P) doubles; 0 for E <= 0 or an unsupported P. */
+size_t dpvo_transform_workspace_bytes(int E, int P);
+
+/* g_coords [E, P, P, 2] -> g_poses [N, 6] (left tangent; every row written)
+   and g_patches [M, 3, P, P]; either may be null (not wanted, not formed).
+   Nothing passes through d' where Z < 0.1; intrinsics get no gradient.  A
+   pose's (patch's) sum over its edges runs in ascending edge order per thread
+   (lane) of its workgroup (wave) and then through a fixed tree.  1 + 1 + 1
+   launches. */
+int dpvo_transform_backward(const float* poses, const float* patches, const float* intrinsics,
+                            const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int P,
+                            int N, int M, const float* g_coords, float* g_poses, float* g_patches,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* train.py:87-88.  coords, coords_gt [E, P, P, 2], valid [E] (of the patch
+   centre).  emin [E]: min over the P P points of |coords - coords_gt| (ties:
+   the lowest point index -> argmin [E]); loss [1]: the mean of emin over the
+   edges with valid > 0.5, count [1] their number.  With no valid edge the
+   loss is 0 (the reference's empty mean is NaN).  One workgroup, one launch. */
+int dpvo_flow_loss_forward(const float* coords, const float* coords_gt, const float* valid, int E,
+                           int P, float* loss, int32_t* count, float* emin, int32_t* argmin,
+                           void* stream);
+
+/* g_coords [E, P, P, 2] = g_loss[0] (x - y) / |x - y| / count at each valid
+   edge's argmin (0 for an exactly-zero difference), 0 everywhere else. */
+int dpvo_flow_loss_backward(const float* coords, const float* coords_gt, const float* valid,
+                            const int32_t* count, const int32_t* argmin, const float* g_loss, int E,
+                            int P, float* g_coords, void* stream);
+
+/* train.py:90-113 for 2 <= n <= 32 poses G, Ps [n, 7].  A_i = inv(G_i) with
+   its translation times s, B_i = inv(Ps_i), s = min(VarA / trace(D), 10) of
+   kabsch_umeyama(t_gt, t_est) (IEEE: a zero trace gives 10), e_ij =
+   Log((A_i^-1 A_j) (B_i^-1 B_j)^-1) for i != j.  out [3] = {mean |e[:3]|,
+   mean |e[3:]|, s}; tr, ro [n (n - 1)]: the pairs in meshgrid 'ij' order
+   with the diagonal removed.  One workgroup, one launch. */
+int dpvo_pose_loss_forward(const float* G, const float* Ps, int n, float* out, float* tr,
+                           float* ro, void* stream);
+
+/* g_out [2] (cotangents of the two means) -> g_G [n, 6], the left-tangent
+   gradient of G; s is a constant; Log through the exact J_l^-1. */
+int dpvo_pose_loss_backward(const float* G, const float* Ps, int n, const float* g_out,
+                            float* g_G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
