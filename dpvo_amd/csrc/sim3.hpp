@@ -27,6 +27,7 @@
 #pragma clang fp contract(off)
 
 // host and device: the same code is unit-tested on the CPU
+// (tests/test_sim3_host.py, every op over every theta / sigma regime)
 #define DPVO_HD __host__ __device__ inline
 
 namespace dpvo {

@@ -5,6 +5,11 @@ tests/sim3_restatement.py, on a synthetic loop with scale drift.
 Measured on an MI355X:
   pgo_residual against the restatement, max abs difference over res / J_i / J_j:
     f64 I/O 7e-14 (bound 1e-9); f32 I/O 1.2e-7 (bound rtol 1e-5, atol 1e-6).
+  the same with residuals chosen from the (theta, sigma) grid of
+  tests/sim3_bands.py (144 edges, theta <= 3, pure scalings included, values up
+  to 8.6): f64 res 1.2e-14, J_i 1.1e-13, J_j 1.3e-13; f32 res 1.2e-7, J_i
+  2.4e-7, J_j 1.9e-7, under the same bounds; 1, 16, 17 and 257 edges through
+  the C ABI leave the rows before and after their outputs untouched.
   run_pgo, f32 poses on the device against the fp64 restatement LM:
     n = 12 / 2 loops: mean square 3.03e-2 -> 5.94e-5 (restatement 5.94e-5, 30
       iterations); re-anchored result differs by 8.3e-7 in translation, 6.1e-8
@@ -227,6 +232,125 @@ def test_pgo_residual_matches_restatement(cb, gpu, case, dtype):
     # jacobian=False: the same residual, bit for bit
     only, = cb.pgo_residual(Gd, Cdd, iii.to(gpu), jjj.to(gpu), False)
     assert torch.equal(only, res)
+
+
+# ---- residuals chosen from the (theta, sigma) grid of tests/sim3_bands.py ----
+def band_edges(res, seed, zero_every=4):
+    """Edges whose residual is the given tangent: gi, gj ~ 0.5 N(0, 1) (every
+    `zero_every`-th edge: gi = gj = 0) and C = Exp(res) Exp(gj) Exp(gi)^-1, so
+    that Log(C Exp(gi) Exp(gj)^-1) = res.  C goes to data by a conversion that
+    is right for any rotation (R.to_data needs w > 0).  Returns (Ginv [2m, 7],
+    C data [m, 8], iii, jjj), fp64; edge e joins poses e and m + e."""
+    import sim3_bands as B
+
+    m = len(res)
+    g = torch.Generator().manual_seed(seed)
+    gi = 0.5 * torch.randn(m, 7, dtype=F64, generator=g)
+    gj = 0.5 * torch.randn(m, 7, dtype=F64, generator=g)
+    gi[::zero_every] = 0
+    gj[::zero_every] = 0
+    C = R.Exp(res) @ R.Exp(gj) @ R.inv(R.Exp(gi))
+    Cd = B.to_data(C)
+    Cd[1::2, 3:7] *= -1  # either sign of the quaternion
+    return torch.cat([gi, gj]), Cd, torch.arange(m), m + torch.arange(m)
+
+
+_BANDS = {}
+
+
+def band_case(name, dtype):
+    """(Ginv, C data, iii, jjj rounded to dtype as fp64; chosen residual; the
+    restatement's res, J_i, J_j at the rounded inputs), computed once."""
+    import sim3_bands as B
+
+    if (name, dtype) not in _BANDS:
+        if name == "grid":  # every (theta <= 3, sigma) point, pure scalings included
+            res, _ = B.grid_tangents(B.THETA[:12], per=1, seed=60)
+            assert len(res) == 144
+            # with zero_every = 5 the gi = gj = 0 edges fall on every sigma column
+            Ginv, Cd, iii, jjj = band_edges(res, 61, zero_every=5)
+        else:  # r edges cycling through a handful of grid points, one per regime
+            pts = [(0.0, 0.501), (0.0, -0.499), (0.0499, 0.501), (0.0501, -0.499), (0.0199, 3.0),
+                   (0.0201, -2.0), (3.0, 0.499), (1e-9, 1e-9), (2.0, -0.501)]
+            r = int(name[1:])
+            res, _ = B.tangents_at([pts[k % len(pts)] for k in range(r)], 1, 62 + r)
+            Ginv, Cd, iii, jjj = band_edges(res, 63 + r)
+        Ginv, Cd = Ginv.to(dtype).double(), Cd.to(dtype).double()
+        C64 = R.from_data(Cd)
+        rres = R.pgo_residual(C64, Ginv[iii], Ginv[jjj])
+        rJi, rJj = R.pgo_jacobians(C64, Ginv[iii], Ginv[jjj])
+        assert torch.isfinite(rres).all() and torch.isfinite(rJi).all() and torch.isfinite(rJj).all()
+        _BANDS[(name, dtype)] = (Ginv, Cd, iii, jjj, res, rres, rJi, rJj)
+    return _BANDS[(name, dtype)]
+
+
+def _band_tol(dtype):
+    return dict(rtol=0, atol=1e-9) if dtype == torch.float64 else dict(rtol=1e-5, atol=1e-6)
+
+
+def test_band_edges_have_the_chosen_residual():
+    """No GPU: the construction above, in the restatement, pure scalings included."""
+    Ginv, Cd, iii, jjj, res, rres, rJi, rJj = band_case("grid", torch.float64)
+    assert int(((res[:, 3:6].norm(dim=1) == 0) & (res[:, 6].abs() >= 0.499)).sum()) == 7
+    assert int((Cd[:, 6] < 0).sum()) > 0  # quaternions of either sign reach the kernel
+    assert float((rres - res).abs().max()) <= 1e-12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+def test_pgo_residual_at_the_bands(cb, gpu, dtype):
+    """Residuals walking theta through 0.02 and 0.05 and sigma through +-0.5,
+    with general and with zero pose tangents."""
+    Ginv, Cd, iii, jjj, _, rres, rJi, rJj = band_case("grid", dtype)
+    Gd, Cdd, ig, jg = Ginv.to(gpu, dtype), Cd.to(gpu, dtype), iii.to(gpu), jjj.to(gpu)
+    res, Ji, Jj = cb.pgo_residual(Gd, Cdd, ig, jg, True)
+    for name, got, ref in (("res", res, rres), ("J_i", Ji, rJi), ("J_j", Jj, rJj)):
+        assert got.dtype == dtype and got.shape == ref.shape
+        got = got.double().cpu()
+        assert torch.isfinite(got).all(), name
+        print("bands", dtype, name, "max abs diff", (got - ref).abs().max().item(),
+              "max abs", ref.abs().max().item())
+        np.testing.assert_allclose(got.numpy(), ref.numpy(), err_msg=name, **_band_tol(dtype))
+    only, = cb.pgo_residual(Gd, Cdd, ig, jg, False)
+    assert torch.equal(only, res)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("r", [1, 16, 17, 257])
+def test_pgo_residual_edge_counts_and_guard_rows(gpu, r, dtype):
+    """The Jacobian kernel takes 16 edges per 256-thread block (16 lanes per
+    edge), the residual-only kernel 256: one edge, a full block, one more, and
+    one more than a block of the residual-only kernel.  Through the C ABI into
+    caller-owned buffers with a sentinel row on either side."""
+    import ctypes
+
+    import dpvo_amd
+
+    lib = dpvo_amd.c_abi()
+    Ginv, Cd, iii, jjj, _, rres, rJi, rJj = band_case(f"r{r}", dtype)
+    Gd, Cdd, ig, jg = Ginv.to(gpu, dtype), Cd.to(gpu, dtype), iii.to(gpu), jjj.to(gpu)
+    sentinel = -777.0
+    buf = {k: torch.full((r + 2, w), sentinel, dtype=dtype, device=gpu)
+           for k, w in (("res", 7), ("Ji", 49), ("Jj", 49), ("only", 7))}
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    code = 2 if dtype == torch.float64 else 0  # DPVO_F64 / DPVO_F32
+    torch.cuda.synchronize(gpu)
+    null = ctypes.c_void_p(None)
+    with torch.cuda.device(gpu):
+        st = lib.dpvo_pgo_residual(ptr(Gd), ptr(Cdd), ptr(ig), ptr(jg), r, len(Ginv), code,
+                                   ptr(buf["res"][1:]), ptr(buf["Ji"][1:]), ptr(buf["Jj"][1:]), null)
+        assert st == 0
+        st = lib.dpvo_pgo_residual(ptr(Gd), ptr(Cdd), ptr(ig), ptr(jg), r, len(Ginv), code,
+                                   ptr(buf["only"][1:]), null, null, null)
+        assert st == 0
+    torch.cuda.synchronize(gpu)
+    for k, t in buf.items():
+        assert bool((t[0] == sentinel).all()) and bool((t[r + 1] == sentinel).all()), k
+    for name, got, ref in (("res", buf["res"], rres), ("J_i", buf["Ji"], rJi), ("J_j", buf["Jj"], rJj)):
+        got = got[1:r + 1].double().cpu().reshape(ref.shape)
+        np.testing.assert_allclose(got.numpy(), ref.numpy(), err_msg=name, **_band_tol(dtype))
+    assert torch.equal(buf["only"], buf["res"])
 
 
 @pytest.mark.gpu

@@ -4,7 +4,13 @@ reference's property tests (dpvo/lietorch/run_tests.py) on the Sim3 class,
 gradients through the class API against the restatement's autograd Jacobians
 at 1e-8 (the derivative is exact here, so the bound is that of SO3 / SE3, not
 the reference's 1e-3 for Sim3), projective_ops.transform with Sim3 poses, and
-the C ABI."""
+the C ABI.
+
+The rows here are general ones plus theta, sigma in {0, 1e-9, 1e-5, 1e-3}.
+The switches of sim3.hpp (theta = 0.02 and 0.05, |sigma| = 0.5), the
+recurrence branch, |sigma| > 0.7, angles next to and beyond pi, w < 0, the
+backward ops through lietorch_backends and f32 backward are swept by
+test_sim3_bands_gpu.py (and test_sim3_host.py on the CPU)."""
 import numpy as np
 import pytest
 import torch
