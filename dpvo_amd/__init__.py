@@ -13,6 +13,8 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
                      the tracker class                   default_config, VONet
   (net.py VONet.forward, train.py loss and step)      -> dpvo_amd.VONet.forward,
                      the training step                   dpvo_amd.training
+  (stream.py image_stream / video_stream)             -> dpvo_amd.stream
+  (evaluate_*.py: evo's association, alignment, ATE)  -> dpvo_amd.evaluation
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -23,7 +25,9 @@ __version__ = "0.1.0"
 
 __all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops", "frontend", "load_extension",
            "c_abi", "BasicEncoder4", "Patchifier", "tracker", "DPVO", "default_config", "VONet", "training",
-           "CorrBlock", "training_schedule", "flow_loss", "pose_loss", "sequence_loss", "train_step"]
+           "CorrBlock", "training_schedule", "flow_loss", "pose_loss", "sequence_loss", "train_step",
+           "stream", "evaluation", "read_calib", "prepare_frame", "ImageStream", "ate", "ATEResult", "read_tum",
+           "write_tum"]
 
 
 def __getattr__(name):  # the classes, without importing torch.nn at package import
@@ -39,6 +43,14 @@ def __getattr__(name):  # the classes, without importing torch.nn at package imp
         from . import training
 
         return getattr(training, name)
+    if name in ("read_calib", "prepare_frame", "ImageStream"):
+        from . import stream
+
+        return getattr(stream, name)
+    if name in ("ate", "ATEResult", "read_tum", "write_tum"):
+        from . import evaluation
+
+        return getattr(evaluation, name)
     if name == "BasicEncoder4":
         from .extractor import BasicEncoder4
 

@@ -70,6 +70,7 @@ def c_abi():
         _lib.dpvo_encoder_saved_bytes.restype = ctypes.c_size_t
         _lib.dpvo_encoder_backward_workspace_bytes.restype = ctypes.c_size_t
         _lib.dpvo_trajectory_workspace_bytes.restype = ctypes.c_size_t
+        _lib.dpvo_trajectory_ate_workspace_bytes.restype = ctypes.c_size_t
     return _lib
 
 

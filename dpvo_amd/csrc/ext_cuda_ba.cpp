@@ -1494,6 +1494,101 @@ std::vector<torch::Tensor> trajectory(torch::Tensor poses, torch::Tensor tstamps
   return {traj, root, info};
 }
 
+// ---- stream.hip / evaluate.hip: frame in, score out ------------------------------
+// Undistort, halve and crop a decoded frame (dpvo/stream.py:24-39, :75-83), one
+// launch -> [image uint8 [3, H, W], intrinsics float32 [4]].  raw: uint8
+// [H0, W0, 3] or [H0, W0]; calib: the 4, 8 or 9 numbers of calib/*.txt.
+std::vector<torch::Tensor> frame_prepare(torch::Tensor raw, std::vector<double> calib,
+                                         double scale, bool swap_rb,
+                                         c10::optional<torch::Tensor> out) {
+  check_device(raw, "raw");
+  TORCH_CHECK(raw.scalar_type() == torch::kUInt8, "frame_prepare: raw must be uint8, got ",
+              raw.scalar_type());
+  TORCH_CHECK(raw.dim() == 2 || (raw.dim() == 3 && raw.size(2) == 3),
+              "frame_prepare: raw must be [H0, W0, 3] or [H0, W0]");
+  TORCH_CHECK(raw.size(0) > 0 && raw.size(1) > 0 && raw.size(0) < (1LL << 31) &&
+                  raw.size(1) < (1LL << 31),
+              "frame_prepare: empty or oversized frame");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(raw.device());
+  raw = raw.contiguous();
+  const int H0 = (int)raw.size(0), W0 = (int)raw.size(1);
+  int H = 0, W = 0;
+  // the count is checked first here only to give dpvo_frame_prepare's own answer for it
+  if (calib.size() == 4 || calib.size() == 8 || calib.size() == 9)
+    check_status(dpvo_frame_prepare_shape(H0, W0, scale, &H, &W), "cuda_ba.frame_prepare");
+  else
+    check_status(DPVO_ERR_UNSUPPORTED, "cuda_ba.frame_prepare (4, 8 or 9 calibration numbers)");
+  torch::Tensor image;
+  if (out && out->defined()) {
+    image = *out;
+    check_device(image, "out");
+    TORCH_CHECK(image.scalar_type() == torch::kUInt8 && image.is_contiguous() &&
+                    image.dim() == 3 && image.size(0) == 3 && image.size(1) == H &&
+                    image.size(2) == W && image.device() == raw.device(),
+                "frame_prepare: out must be a contiguous uint8 [3, ", H, ", ", W,
+                "] tensor on raw's device");
+  } else {
+    image = torch::empty({3, H, W}, raw.options());
+  }
+  auto intr = torch::empty({4}, raw.options().dtype(torch::kFloat32));
+  check_status(dpvo_frame_prepare(raw.data_ptr<uint8_t>(), H0, W0, raw.dim() == 2 ? 1 : 3,
+                                  calib.data(), (int)calib.size(), scale, swap_rb ? 1 : 0,
+                                  image.data_ptr<uint8_t>(), intr.data_ptr<float>(),
+                                  current_stream()),
+               "cuda_ba.frame_prepare");
+  return {image, intr};
+}
+
+// ATE of an estimated trajectory against a reference one (evaluate_euroc.py:109-119
+// through evo), one launch -> [stats f64[8], model f64[13], pairs i32[min(n, m), 2],
+// status i32[1]]
+std::vector<torch::Tensor> trajectory_ate(torch::Tensor est_xyz, torch::Tensor est_t,
+                                          torch::Tensor ref_xyz, torch::Tensor ref_t,
+                                          double max_diff, bool align) {
+  check_device(est_xyz, "est_xyz");
+  check_device(est_t, "est_t");
+  check_device(ref_xyz, "ref_xyz");
+  check_device(ref_t, "ref_t");
+  TORCH_CHECK(est_xyz.scalar_type() == torch::kFloat32 || est_xyz.scalar_type() == torch::kFloat64,
+              "trajectory_ate: est_xyz must be float32 or float64");
+  TORCH_CHECK(est_t.scalar_type() == torch::kFloat64 && ref_xyz.scalar_type() == torch::kFloat64 &&
+                  ref_t.scalar_type() == torch::kFloat64,
+              "trajectory_ate: est_t, ref_xyz and ref_t must be float64");
+  TORCH_CHECK(est_xyz.dim() == 2 && est_xyz.size(1) == 3 && est_t.dim() == 1 &&
+                  est_t.size(0) == est_xyz.size(0),
+              "trajectory_ate: est_xyz [n, 3], est_t [n]");
+  TORCH_CHECK(ref_xyz.dim() == 2 && ref_xyz.size(1) == 3 && ref_t.dim() == 1 &&
+                  ref_t.size(0) == ref_xyz.size(0),
+              "trajectory_ate: ref_xyz [m, 3], ref_t [m]");
+  TORCH_CHECK(est_xyz.device() == est_t.device() && est_xyz.device() == ref_xyz.device() &&
+                  est_xyz.device() == ref_t.device(),
+              "trajectory_ate: tensors on different devices");
+  const int64_t n = est_xyz.size(0), m = ref_xyz.size(0);
+  TORCH_CHECK(n >= 1 && m >= 1, "trajectory_ate: empty trajectory");
+  TORCH_CHECK(n < (1LL << 31) && m < (1LL << 31), "trajectory_ate: trajectory too long");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(est_xyz.device());
+  est_xyz = est_xyz.contiguous();
+  est_t = est_t.contiguous();
+  ref_xyz = ref_xyz.contiguous();
+  ref_t = ref_t.contiguous();
+  const auto f64 = ref_xyz.options();
+  const auto i32 = ref_xyz.options().dtype(torch::kInt32);
+  auto stats = torch::empty({8}, f64);
+  auto model = torch::empty({13}, f64);
+  auto pairs = torch::empty({std::min(n, m), 2}, i32);
+  auto status = torch::empty({1}, i32);
+  const size_t wsb = dpvo_trajectory_ate_workspace_bytes((int)n, (int)m);
+  auto ws = torch::empty({(int64_t)(wsb / sizeof(double))}, f64);
+  check_status(dpvo_trajectory_ate(est_xyz.data_ptr(), dtype_code(est_xyz),
+                                   est_t.data_ptr<double>(), (int)n, ref_xyz.data_ptr<double>(),
+                                   ref_t.data_ptr<double>(), (int)m, max_diff, align ? 1 : 0,
+                                   stats.data_ptr<double>(), model.data_ptr<double>(),
+                                   pairs.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
+                                   ws.data_ptr(), wsb, current_stream()),
+               "cuda_ba.trajectory_ate");
+  return {stats, model, pairs, status};
+}
+
 // ---- tracker.hip: the small kernels of the tracker's frame path ----------------
 static int ring_dtype(const torch::Tensor& t, const char* name) {
   check_device(t, name);
@@ -1811,6 +1906,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("poses"), py::arg("tstamps"), py::arg("n"), py::arg("n_dev"),
         py::arg("delta_log"), py::arg("delta_pairs"), py::arg("delta_count"), py::arg("counter"),
         py::arg("inverse"));
+  m.def("frame_prepare", &frame_prepare,
+        "undistort, halve and crop a decoded frame (dpvo/stream.py), one launch -> "
+        "[image uint8 [3, H, W], intrinsics float32 [4]]",
+        py::arg("raw"), py::arg("calib"), py::arg("scale") = 1.0, py::arg("swap_rb") = false,
+        py::arg("out") = py::none());
+  m.def("trajectory_ate", &trajectory_ate,
+        "association, Sim(3) alignment and error statistics of two trajectories, one launch -> "
+        "[stats f64[8], model f64[13], pairs i32[min(n, m), 2], status i32[1]]",
+        py::arg("est_xyz"), py::arg("est_t"), py::arg("ref_xyz"), py::arg("ref_t"),
+        py::arg("max_diff") = 0.01, py::arg("align") = true);
   m.def("frame_sample", &frame_sample,
         "Patchifier's gathers (net.py:388-399) and the ring / colour writes of DPVO.__call__ "
         "(dpvo.py:937-938, 965-969) of frame n, one launch",

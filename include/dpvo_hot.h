@@ -689,6 +689,76 @@ int dpvo_trajectory(const float* poses, const int64_t* tstamps, int N, int n, co
                     float* traj, int64_t* root, int32_t* info, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------- image stream and evaluation */
+
+/* The front of a run on a sequence as it sits on disk (dpvo/stream.py:24-39,
+   :75-83): undistort, halve and crop one decoded frame in one launch, no host
+   synchronisation, no state between calls.
+     raw        uint8 [H0, W0, channels] on the device, channels 3 (interleaved,
+                as a decoder delivers it) or 1 (grey, replicated into the three
+                planes as cv2.imread does)
+     calib      ncalib host doubles fx fy cx cy [k1 k2 p1 p2 [k3]] (calib/*.txt)
+     scale      1 or 0.5 (0.5 needs even H0 and W0)
+     image      uint8 [3, H, W] planar, H = H1 - H1 % 16, W = W1 - W1 % 16 of
+                (H1, W1) = (H0, W0) scale, cropped top-left; plane p = channel p,
+                or 2 - p with swap_rb.  4-byte aligned.
+     intrinsics float32 [4] on the device = (fx, fy, cx, cy) scale
+   ncalib 4: no remap (the reference's len(calib) > 4).  ncalib 8 / 9: pixel
+   (u, v) of the undistorted H0 x W0 image is, in fp64, in this order, without
+   FMA contraction,
+     x = (u - cx)/fx;  y = (v - cy)/fy;  r2 = x*x + y*y
+     kr = 1 + r2*(k1 + r2*(k2 + r2*k3))
+     xd = x*kr + (2*p1*x*y + p2*(r2 + 2*x*x))
+     yd = y*kr + (p1*(r2 + 2*y*y) + 2*p2*x*y)
+     mx = fx*xd + cx;  my = fy*yd + cy
+     qx = floor(mx*32 + 0.5);  qy = floor(my*32 + 0.5)   (clamped to +-2^30, NaN low)
+     ix = qx >> 5, ax = qx & 31;  iy = qy >> 5, ay = qy & 31
+     val = ((32-ax)(32-ay) S[iy,ix] + ax(32-ay) S[iy,ix+1]
+          + (32-ax)ay S[iy+1,ix] + ax ay S[iy+1,ix+1] + 512) >> 10
+   with S = 0 outside the source (BORDER_CONSTANT).  At scale 0.5 an output
+   pixel is (a + b + c + d + 2) >> 2 over the 2 x 2 block of those rounded
+   values (undistort, then INTER_AREA).  OpenCV's camera model with its 1/32
+   pixel map quantisation; not claimed bit-equal to cv2.undistort.
+   Null pointers, non-positive sizes, channels other than 1 / 3, a misaligned
+   image, fx or fy zero or not finite: DPVO_ERR_INVALID; ncalib other than
+   4 / 8 / 9, another scale, an odd size at 0.5, a side above 16384 or an empty
+   output: DPVO_ERR_UNSUPPORTED; all before any launch.
+   dpvo_frame_prepare_shape gives (H, W) with the same size checks. */
+int dpvo_frame_prepare_shape(int H0, int W0, double scale, int* H, int* W);
+int dpvo_frame_prepare(const uint8_t* raw, int H0, int W0, int channels, const double* calib,
+                       int ncalib, double scale, int swap_rb, uint8_t* image, float* intrinsics,
+                       void* stream);
+
+/* Absolute trajectory error of an estimated trajectory against a reference
+   one (evaluate_euroc.py:109-119 through evo): association by timestamp,
+   Sim(3) Umeyama alignment, error statistics.  One launch of one workgroup, no
+   host synchronisation; every reduction has a fixed order (run-to-run
+   bit-identical).  All pointers but the workspace are device arrays:
+     est_xyz [n, 3] (est_dtype DPVO_F32 / DPVO_F64; arithmetic is fp64),
+     est_t [n], ref_xyz [m, 3], ref_t [m] fp64; stamps non-decreasing.
+   Association: the long side is est if n > m, else ref.  Every stamp of the
+   short side takes the long stamp with the smallest |dt| (ties: the lower
+   index) and the pair is kept iff |dt| <= max_diff; pairs stay in short-side
+   order, a long index may repeat.
+   Alignment (align = 1): y ~ c R x + t, x = est, y = ref, by Umeyama's fit on
+   the centred moments of the pairs (scale corrected); align = 0: c = 1, R = I,
+   t = 0.  Errors e_i = |c R x_i + t - y_i|.
+     stats  fp64 [8] = rmse, mean, median (np.median), std (population), min,
+            max, sse, count
+     model  fp64 [13] = R (row-major), t, c
+     pairs  int32 [min(n, m), 2] = (est index, ref index), unused rows -1
+     status int32 [1]: bit 0 fewer than 3 pairs, bit 1 degenerate covariance,
+            bit 2 unsorted (or NaN) stamps: nothing is associated, count 0.
+   On any set bit stats[0..6] are NaN, count is still written and model is the
+   identity.  Null pointers, n or m < 1, max_diff negative or NaN, align other
+   than 0 / 1: DPVO_ERR_INVALID; another est_dtype, n or m above 65536:
+   DPVO_ERR_UNSUPPORTED; short workspace: DPVO_ERR_WORKSPACE (in that order). */
+size_t dpvo_trajectory_ate_workspace_bytes(int n, int m);
+int dpvo_trajectory_ate(const void* est_xyz, int est_dtype, const double* est_t, int n,
+                        const double* ref_xyz, const double* ref_t, int m, double max_diff,
+                        int align, double* stats, double* model, int32_t* pairs, int32_t* status,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ tracker */
 
 /* The four small kernels of the tracker's frame path (dpvo_amd/dpvo.py), one
