@@ -1303,6 +1303,114 @@ __device__ void reduce_acc(const double* acc, double* red, v4u* gout, unsigned l
   }
 }
 
+// Apply the dX of iteration it - 1 (L.dX): poses retracted (pose_retr_kernel,
+// ba_cuda.cu:178-206), inverse depths dZ = Q (u - E^T dX) (:563) with
+// patch_retr's clamps (:209-229).  The two chains are independent -- the poses
+// read dX and L.pose, the depths dX, the E entries, L.qu and L.dbase / L.dep --
+// so they start on different waves: pose i on thread i (wave 0), relevant
+// patch ri on thread (64 + ri) mod 256.  Which thread computes a value does
+// not enter its arithmetic.
+//   final == false (between iterations): every workgroup needs all N poses
+//     and all its relevant patches for the next linearisation: results to
+//     L.pose / L.dep, then a barrier.
+//   final == true (after the last iteration): only what leaves the kernel --
+//     workgroup 0 retracts the poses, every workgroup its owned patches
+//     (pkx >= 0) -- and the thread that has a value stores it to A.poses /
+//     A.patches itself; L.pose / L.dep are not written, no barrier follows.
+// `final` is a constant at both call sites; every barrier below is on a
+// workgroup-uniform path (final, L.ej, nrel and region_b are uniform).
+__device__ __forceinline__ void apply_dx(const WArgs& A, const WL& L, int tid, int g, int N, int PP,
+                                         int nrel, int it, int t0w, size_t region_b, int nrp,
+                                         bool final) {
+  if (!final || g == 0)
+    for (int i = tid; i < N; i += kWT) {
+      float xi[6], tt[3], qq[4], t1[3], q1[4];
+#pragma unroll
+      for (int k = 0; k < 6; k++) xi[k] = (float)L.dX[6 * i + k];
+      float* pl = L.pose + 8 * i;
+      tt[0] = pl[0]; tt[1] = pl[1]; tt[2] = pl[2];
+      qq[0] = pl[3]; qq[1] = pl[4]; qq[2] = pl[5]; qq[3] = pl[6];
+      retrSE3(xi, tt, qq, t1, q1);
+      if (final) {
+        const int gp = t0w + i;
+        if (gp < 0 || gp >= A.num_poses) continue;
+        pl = A.poses + 7 * (size_t)gp;
+      }
+      pl[0] = t1[0]; pl[1] = t1[1]; pl[2] = t1[2];
+      pl[3] = q1[0]; pl[4] = q1[1]; pl[5] = q1[2]; pl[6] = q1[3];
+    }
+  if (final) {
+    mark(A, 48);  // final-apply sub-phases (instrumentation): poses retracted
+    if (A.marks && g == 0 && tid == 0) {
+      A.marks[52] = nrp;
+      A.marks[53] = (L.ej ? 2 : 1);  // E entries in LDS, else in the HBM buffer
+    }
+    mark(A, 49);
+  }
+  // relevant patch ri, E^T dX = ex: its new inverse depth, to L.dep or (final)
+  // to all PP elements of the patch
+  auto put_depth = [&](int ri, double ex) {
+    const double2 qu = L.qu[ri];
+    const float dz = (float)(qu.x * (qu.y - ex));
+    const float base = (it == 1) ? L.dbase[ri] : L.dep[ri];
+    float d = base + dz;
+    d = (d > 20.0f) ? 1.0f : d;
+    d = (float)fmax((double)d, 1e-4);
+    if (final) {
+      float* out = A.patches + (size_t)L.pkx[ri] * 3 * PP + 2 * PP;
+      for (int c = 0; c < PP; c++) out[c] = d;
+    } else {
+      L.dep[ri] = d;
+    }
+  };
+  // In the final apply with the E entries in HBM, kTP threads per owned patch:
+  // each sums E^T dX over a contiguous part of the patch's edges
+  // (patch_etdx's per-edge order inside the part), the parts are added in
+  // part order -- one HBM round trip of E entries instead of one per 4
+  // edges of a ~18-edge patch on a single thread
+  constexpr int kTP = 8;
+  // region: olist [nrel + 1] (owned flags -> prefix), oidx [nrel], opart [owned][kTP]
+  const size_t opart_at = al16(sizeof(int) * (2 * (size_t)nrel + 1));
+  if (!final || L.ej || opart_at + sizeof(double) * kTP * (size_t)nrel > region_b) {
+    // between iterations; E entries in LDS (short patches, cfg2-like windows);
+    // or more relevant patches than the region holds parts for: one thread per patch
+    for (int ri = (tid - 64) & (kWT - 1); ri < nrel; ri += kWT) {
+      if (final && L.pkx[ri] < 0) continue;
+      put_depth(ri, patch_etdx(L, A, ri, (it - 1) & 1, N));
+    }
+  } else {
+    int* olist = reinterpret_cast<int*>(L.region);
+    double* opart = reinterpret_cast<double*>(L.region + opart_at);
+    for (int ri = tid; ri < nrel; ri += kWT) olist[ri] = L.pkx[ri] >= 0 ? 1 : 0;
+    __syncthreads();
+    const int nown = fscan(olist, nrel, L.ctl + cScan);  // olist[ri] = owned patches before ri
+    // compact: owned patch k -> relevant index (stored after the prefix array)
+    int* oidx = olist + nrel + 1;
+    for (int ri = tid; ri < nrel; ri += kWT)
+      if (L.pkx[ri] >= 0) oidx[olist[ri]] = ri;
+    __syncthreads();
+    for (int t = (tid - 64) & (kWT - 1); t < nown * kTP; t += kWT) {
+      const int k = t / kTP, part = t % kTP, ri = oidx[k];
+      const int qa = L.roff[ri], qz = L.roff[ri + 1], len = (qz - qa + kTP - 1) / kTP;
+      const int q0 = min(qa + part * len, qz), q1 = min(q0 + len, qz);
+      opart[t] = edges_etdx(L, A, q0, q1, (it - 1) & 1, N);
+    }
+    __syncthreads();
+    for (int k = (tid - 64) & (kWT - 1); k < nown; k += kWT) {
+      double ex = 0.0;
+#pragma unroll
+      for (int part = 0; part < kTP; part++) ex += opart[k * kTP + part];
+      put_depth(oidx[k], ex);
+    }
+  }
+  if (!final) {
+    __syncthreads();
+  } else {
+    if (A.marks) __syncthreads();  // (instrumentation: the stamp is the workgroup's last depth)
+    mark(A, 50);  // depths updated and stored
+  }
+}
+
 __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, g = blockIdx.x;
@@ -1808,30 +1916,8 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   for (int it = 0; it < A.iters; it++) {
     const int tid = opaque_tid();  // (shadows the kernel's: see opaque_tid)
     const int mb = 2 + 8 * it;
-    if (it > 0) {
-      // ---- apply dX of iteration it-1: poses, then inverse depths ----
-      for (int i = tid; i < N; i += kWT) {  // pose_retr_kernel (:178-206)
-        float xi[6], tt[3], qq[4], t1[3], q1[4];
-#pragma unroll
-        for (int k = 0; k < 6; k++) xi[k] = (float)L.dX[6 * i + k];
-        float* pl = L.pose + 8 * i;
-        tt[0] = pl[0]; tt[1] = pl[1]; tt[2] = pl[2];
-        qq[0] = pl[3]; qq[1] = pl[4]; qq[2] = pl[5]; qq[3] = pl[6];
-        retrSE3(xi, tt, qq, t1, q1);
-        pl[0] = t1[0]; pl[1] = t1[1]; pl[2] = t1[2];
-        pl[3] = q1[0]; pl[4] = q1[1]; pl[5] = q1[2]; pl[6] = q1[3];
-      }
-      for (int ri = tid; ri < nrel_e; ri += kWT) {  // dZ = Q (u - E^T dX) (:563), patch_retr (:209-229)
-        const double ex = patch_etdx(L, A, ri, (it - 1) & 1, N);
-        const double2 qu = L.qu[ri];
-        const float dz = (float)(qu.x * (qu.y - ex));
-        const float base = (it == 1) ? L.dbase[ri] : L.dep[ri];
-        float d = base + dz;
-        d = (d > 20.0f) ? 1.0f : d;
-        L.dep[ri] = (float)fmax((double)d, 1e-4);
-      }
-      __syncthreads();
-    }
+    // ---- apply dX of iteration it-1: poses and inverse depths, for the next linearisation ----
+    if (it > 0) apply_dx(A, L, tid, g, N, PP, nrel_e, it, t0w, region_b, nrp, false);
     // ---- linearise + assemble this workgroup's block ----
     double acc[36];
     int nact = kWT;  // threads that can hold nonzero acc (assemble)
@@ -1983,96 +2069,7 @@ __global__ void __launch_bounds__(kWT) ba_window_kernel(WArgs A) {
   }
 
   // ---------------- final apply + write-back ----------------
-  if (A.iters > 0) {
-    const int it = A.iters;
-    for (int i = tid; i < N; i += kWT) {
-      float xi[6], tt[3], qq[4], t1[3], q1[4];
-#pragma unroll
-      for (int k = 0; k < 6; k++) xi[k] = (float)L.dX[6 * i + k];
-      float* pl = L.pose + 8 * i;
-      tt[0] = pl[0]; tt[1] = pl[1]; tt[2] = pl[2];
-      qq[0] = pl[3]; qq[1] = pl[4]; qq[2] = pl[5]; qq[3] = pl[6];
-      retrSE3(xi, tt, qq, t1, q1);
-      pl[0] = t1[0]; pl[1] = t1[1]; pl[2] = t1[2];
-      pl[3] = q1[0]; pl[4] = q1[1]; pl[5] = q1[2]; pl[6] = q1[3];
-    }
-    mark(A, 48);  // final-apply sub-phases (instrumentation): poses retracted
-    if (A.marks && g == 0 && tid == 0) {
-      A.marks[52] = nrp;
-      A.marks[53] = (L.ej ? 2 : 1);  // E entries in LDS, else in the HBM buffer
-    }
-    mark(A, 49);
-    {
-      // the depths this workgroup writes (owned patches); with the E entries
-      // in HBM, kTP threads per patch: each sums E^T dX over a contiguous
-      // part of the patch's edges
-      // (patch_etdx's per-edge order inside the part), the parts are added in
-      // part order -- one HBM round trip of E entries instead of one per 4
-      // edges of a ~18-edge patch on a single thread
-      constexpr int kTP = 8;
-      // region: olist [nrel + 1] (owned flags -> prefix), oidx [nrel], opart [owned][kTP]
-      int* olist = reinterpret_cast<int*>(L.region);
-      double* opart = reinterpret_cast<double*>(L.region + al16(sizeof(int) * (2 * (size_t)nrel_e + 1)));
-      if (L.ej ||
-          al16(sizeof(int) * (2 * (size_t)nrel_e + 1)) + sizeof(double) * kTP * (size_t)nrel_e > region_b) {
-        // E entries in LDS (short patches, cfg2-like windows), or more relevant
-        // patches than the region holds parts for: one thread per patch
-        for (int ri = tid; ri < nrel_e; ri += kWT) {
-          if (L.pkx[ri] < 0) continue;
-          const double ex = patch_etdx(L, A, ri, (it - 1) & 1, N);
-          const double2 qu = L.qu[ri];
-          const float dz = (float)(qu.x * (qu.y - ex));
-          const float base = (it == 1) ? L.dbase[ri] : L.dep[ri];
-          float d = base + dz;
-          d = (d > 20.0f) ? 1.0f : d;
-          L.dep[ri] = (float)fmax((double)d, 1e-4);
-        }
-        olist = nullptr;
-      }
-      if (olist) {
-      for (int ri = tid; ri < nrel_e; ri += kWT) olist[ri] = L.pkx[ri] >= 0 ? 1 : 0;
-      __syncthreads();
-      const int nown = fscan(olist, nrel_e, ctl + cScan);  // olist[ri] = owned patches before ri
-      // compact: owned patch k -> relevant index (stored after the prefix array)
-      int* oidx = olist + nrel_e + 1;
-      for (int ri = tid; ri < nrel_e; ri += kWT)
-        if (L.pkx[ri] >= 0) oidx[olist[ri]] = ri;
-      __syncthreads();
-      for (int t = tid; t < nown * kTP; t += kWT) {
-        const int k = t / kTP, part = t % kTP, ri = oidx[k];
-        const int qa = L.roff[ri], qz = L.roff[ri + 1], len = (qz - qa + kTP - 1) / kTP;
-        const int q0 = min(qa + part * len, qz), q1 = min(q0 + len, qz);
-        opart[t] = edges_etdx(L, A, q0, q1, (it - 1) & 1, N);
-      }
-      __syncthreads();
-      for (int k = tid; k < nown; k += kWT) {
-        const int ri = oidx[k];
-        double ex = 0.0;
-#pragma unroll
-        for (int part = 0; part < kTP; part++) ex += opart[k * kTP + part];
-        const double2 qu = L.qu[ri];
-        const float dz = (float)(qu.x * (qu.y - ex));
-        const float base = (it == 1) ? L.dbase[ri] : L.dep[ri];
-        float d = base + dz;
-        d = (d > 20.0f) ? 1.0f : d;
-        L.dep[ri] = (float)fmax((double)d, 1e-4);
-      }
-      }
-    }
-    __syncthreads();
-    mark(A, 50);  // depths updated
-    for (int k = tid; k < nrel_e * PP; k += kWT) {
-      const int ri = k / PP, c = k % PP;
-      const int kx = L.pkx[ri];
-      if (kx >= 0) A.patches[(size_t)kx * 3 * PP + 2 * PP + c] = L.dep[ri];
-    }
-    if (g == 0)
-      for (int i = tid; i < N; i += kWT) {
-        const int gp = t0w + i;
-        if (gp >= 0 && gp < A.num_poses)
-          for (int c = 0; c < 7; c++) A.poses[7 * (size_t)gp + c] = L.pose[8 * i + c];
-      }
-  }
+  if (A.iters > 0) apply_dx(A, L, tid, g, N, PP, nrel_e, A.iters, t0w, region_b, nrp, true);
   if (tid == 0) {
     int st = 0;
     if (ctl[cTimeout]) st |= kStTimeout;
