@@ -15,6 +15,7 @@ Drop-in replacements for cuteboyqq/DPVO's native surface:
                      the training step                   dpvo_amd.training
   (stream.py image_stream / video_stream)             -> dpvo_amd.stream
   (evaluate_*.py: evo's association, alignment, ATE)  -> dpvo_amd.evaluation
+  (data_readers/: frame graph, augmentation, TartanAir) -> dpvo_amd.data_readers
 
 Importing the package puts the in-tree native build on sys.path, so code
 written against the reference (`import cuda_corr`) runs the HIP kernels.
@@ -27,7 +28,9 @@ __all__ = ["altcorr", "fastba", "lietorch", "net", "extractor", "projective_ops"
            "c_abi", "BasicEncoder4", "Patchifier", "tracker", "DPVO", "default_config", "VONet", "training",
            "CorrBlock", "training_schedule", "flow_loss", "pose_loss", "sequence_loss", "train_step",
            "stream", "evaluation", "read_calib", "prepare_frame", "ImageStream", "ate", "ATEResult", "read_tum",
-           "write_tum"]
+           "write_tum", "data_readers", "frame_distance_matrix", "build_frame_graph", "FrameGraph",
+           "sample_sequence", "AugmentParams", "RGBDAugmentor", "normalize_depth", "RGBDDataset",
+           "TartanAir"]
 
 
 def __getattr__(name):  # the classes, without importing torch.nn at package import
@@ -51,6 +54,11 @@ def __getattr__(name):  # the classes, without importing torch.nn at package imp
         from . import evaluation
 
         return getattr(evaluation, name)
+    if name in ("frame_distance_matrix", "build_frame_graph", "FrameGraph", "sample_sequence",
+                "AugmentParams", "RGBDAugmentor", "normalize_depth", "RGBDDataset", "TartanAir"):
+        from . import data_readers
+
+        return getattr(data_readers, name)
     if name == "BasicEncoder4":
         from .extractor import BasicEncoder4
 

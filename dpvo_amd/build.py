@@ -34,7 +34,7 @@ ARCH = os.environ.get("DPVO_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["corr.hip", "corr_nhwc.hip", "corr_nchw.hip", "ba.hip", "ba_window.hip", "ba_large.hip", "lie.hip", "pgo.hip", "pg.hip",
                "keyframe.hip", "spd_solve.hip", "ransac.hip", "update_op.hip", "update_bwd.hip", "encoder.hip", "encoder_bwd.hip",
-               "frontend.hip", "ba_layer.hip", "tracker.hip", "match.hip", "triangulate.hip", "train.hip", "stream.hip", "evaluate.hip"]
+               "frontend.hip", "ba_layer.hip", "tracker.hip", "match.hip", "triangulate.hip", "train.hip", "stream.hip", "evaluate.hip", "dataset.hip"]
 EXTENSIONS = {
     "cuda_corr": "ext_cuda_corr.cpp",
     "cuda_ba": "ext_cuda_ba.cpp",
@@ -43,7 +43,7 @@ EXTENSIONS = {
     "dpvo_encoder": "ext_encoder.cpp",
 }
 HEADERS = ["common.hpp", "ext_common.hpp", "ba_device.hpp", "ba_solve.hpp", "pyr_insert.hpp", "ba_bgj.hpp",
-           "sim3.hpp", "lie_se3.hpp", "ba_paths.hpp", "corr_paths.hpp", "encoder_layout.hpp", "update_layout.hpp", "umeyama.hpp"]
+           "sim3.hpp", "lie_se3.hpp", "ba_paths.hpp", "corr_paths.hpp", "encoder_layout.hpp", "update_layout.hpp", "umeyama.hpp", "radix_select.hpp"]
 # per-source device flags.  The BA window kernel is a chain of short dependent
 # steps run by few waves: clang's SLP vectoriser packs its scalar fp32 math into
 # v_pk_fma_f32 and pays for it with register-pair v_mov shuffles (3x the

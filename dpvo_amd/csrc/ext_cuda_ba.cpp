@@ -1589,6 +1589,137 @@ std::vector<torch::Tensor> trajectory_ate(torch::Tensor est_xyz, torch::Tensor e
   return {stats, model, pairs, status};
 }
 
+// ---- dataset.hip: the device half of the training data readers -------------------
+static torch::Tensor data_f32(const torch::Tensor& t, const char* name) {
+  check_device(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be float32, got ", t.scalar_type());
+  return t.contiguous();
+}
+
+// rgbd_utils.compute_distance_matrix_flow: poses [N, 7] (world-from-camera), disps
+// [N, h, w], intrinsics [N, 4] -> D float32 [N, N], one launch
+torch::Tensor frame_flow_distance(torch::Tensor poses, torch::Tensor disps,
+                                  torch::Tensor intrinsics) {
+  poses = data_f32(poses, "poses");
+  disps = data_f32(disps, "disps");
+  intrinsics = data_f32(intrinsics, "intrinsics");
+  TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7 && poses.size(0) >= 1,
+              "frame_flow_distance: poses must be [N, 7]");
+  const int64_t N = poses.size(0);
+  TORCH_CHECK(disps.dim() == 3 && disps.size(0) == N && disps.size(1) >= 1 && disps.size(2) >= 1,
+              "frame_flow_distance: disps must be [N, h, w]");
+  TORCH_CHECK(intrinsics.dim() == 2 && intrinsics.size(0) == N && intrinsics.size(1) == 4,
+              "frame_flow_distance: intrinsics must be [N, 4]");
+  TORCH_CHECK(poses.device() == disps.device() && poses.device() == intrinsics.device(),
+              "frame_flow_distance: tensors on different devices");
+  TORCH_CHECK(N < (1LL << 31) && disps.size(1) < (1LL << 31) && disps.size(2) < (1LL << 31),
+              "frame_flow_distance: too large");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(poses.device());
+  auto D = torch::empty({N, N}, poses.options());
+  check_status(dpvo_frame_flow_distance(poses.data_ptr<float>(), disps.data_ptr<float>(),
+                                        intrinsics.data_ptr<float>(), (int)N, (int)disps.size(1),
+                                        (int)disps.size(2), D.data_ptr<float>(), current_stream()),
+               "cuda_ba.frame_flow_distance");
+  return D;
+}
+
+// base.py:77-80 as CSR -> [rowptr i32 [N + 1], col i32 [nnz], dist f32 [nnz]].
+// One host read (nnz) sizes the outputs: a build step, not a per-frame call.
+std::vector<torch::Tensor> frame_graph(torch::Tensor D, double f, double max_flow) {
+  D = data_f32(D, "D");
+  TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1) && D.size(0) >= 1 && D.size(0) < (1LL << 31),
+              "frame_graph: D must be [N, N]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(D.device());
+  const int N = (int)D.size(0);
+  const auto i32 = D.options().dtype(torch::kInt32);
+  auto rowptr = torch::empty({(int64_t)N + 1}, i32);
+  check_status(dpvo_frame_graph_count(D.data_ptr<float>(), N, (float)f, (float)max_flow,
+                                      rowptr.data_ptr<int32_t>(), current_stream()),
+               "cuda_ba.frame_graph (count)");
+  const int nnz = rowptr[N].item<int32_t>();
+  auto col = torch::empty({(int64_t)nnz}, i32);
+  auto dist = torch::empty({(int64_t)nnz}, D.options());
+  check_status(dpvo_frame_graph_fill(D.data_ptr<float>(), N, (float)f, (float)max_flow,
+                                     rowptr.data_ptr<int32_t>(), nnz ? col.data_ptr<int32_t>() : nullptr,
+                                     nnz ? dist.data_ptr<float>() : nullptr, nnz, current_stream()),
+               "cuda_ba.frame_graph (fill)");
+  return {rowptr, col, dist};
+}
+
+// augmentation.py with the random draws given -> [images [N, 3, ch, cw], disps
+// [N, ch, cw], intrinsics [N, 4]]
+std::vector<torch::Tensor> rgbd_augment(torch::Tensor images, torch::Tensor disps,
+                                        torch::Tensor intrinsics, int64_t crop_h, int64_t crop_w,
+                                        bool do_color, std::vector<int64_t> order, double brightness,
+                                        double contrast, double saturation, double hue, bool gray,
+                                        bool invert, double scale, bool swap_rb) {
+  images = data_f32(images, "images");
+  disps = data_f32(disps, "disps");
+  intrinsics = data_f32(intrinsics, "intrinsics");
+  TORCH_CHECK(images.dim() == 4 && images.size(1) == 3 && images.size(0) >= 1,
+              "rgbd_augment: images must be [N, 3, H, W]");
+  const int64_t N = images.size(0), H = images.size(2), W = images.size(3);
+  TORCH_CHECK(disps.dim() == 3 && disps.size(0) == N && disps.size(1) == H && disps.size(2) == W,
+              "rgbd_augment: disps must be [N, H, W]");
+  TORCH_CHECK(intrinsics.dim() == 2 && intrinsics.size(0) == N && intrinsics.size(1) == 4,
+              "rgbd_augment: intrinsics must be [N, 4]");
+  TORCH_CHECK(images.device() == disps.device() && images.device() == intrinsics.device(),
+              "rgbd_augment: tensors on different devices");
+  TORCH_CHECK(order.size() == 4, "rgbd_augment: order must hold four operations");
+  TORCH_CHECK(N < (1LL << 31) && H >= 1 && W >= 1 && H < (1LL << 31) && W < (1LL << 31) &&
+                  crop_h >= 1 && crop_w >= 1 && crop_h < (1LL << 31) && crop_w < (1LL << 31),
+              "rgbd_augment: empty or oversized");
+  dpvo_augment_params p;
+  p.do_color = do_color ? 1 : 0;
+  for (int k = 0; k < 4; k++)
+    p.order[k] = (order[k] >= 0 && order[k] <= 3) ? (int)order[k] : -1;
+  p.brightness = (float)brightness;
+  p.contrast = (float)contrast;
+  p.saturation = (float)saturation;
+  p.hue = (float)hue;
+  p.gray = gray ? 1 : 0;
+  p.invert = invert ? 1 : 0;
+  p.scale = scale;
+  p.swap_rb = swap_rb ? 1 : 0;
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(images.device());
+  auto images_out = torch::empty({N, 3, crop_h, crop_w}, images.options());
+  auto disps_out = torch::empty({N, crop_h, crop_w}, images.options());
+  auto intr_out = torch::empty({N, 4}, images.options());
+  const size_t wsb = dpvo_rgbd_augment_workspace_bytes((int)N, (int)H, (int)W);
+  // the scratch image is touched only by colour followed by resampling
+  const size_t need = (do_color && scale != 1.0) ? wsb : 8 * 256;
+  auto ws = torch::empty({(int64_t)((need + 7) / sizeof(double))},
+                         images.options().dtype(torch::kFloat64));
+  check_status(dpvo_rgbd_augment(images.data_ptr<float>(), disps.data_ptr<float>(),
+                                 intrinsics.data_ptr<float>(), (int)N, (int)H, (int)W, (int)crop_h,
+                                 (int)crop_w, &p, images_out.data_ptr<float>(),
+                                 disps_out.data_ptr<float>(), intr_out.data_ptr<float>(),
+                                 ws.data_ptr(), need, current_stream()),
+               "cuda_ba.rgbd_augment");
+  return {images_out, disps_out, intr_out};
+}
+
+// base.py:171-173 -> [disps / s, poses with the translation times s, (s, lo, hi) f32 [3]]
+std::vector<torch::Tensor> normalize_depth(torch::Tensor disps, torch::Tensor poses) {
+  disps = data_f32(disps, "disps");
+  poses = data_f32(poses, "poses");
+  TORCH_CHECK(disps.numel() >= 1 && disps.numel() < (1LL << 31), "normalize_depth: disps is empty or too large");
+  TORCH_CHECK(poses.dim() >= 1 && poses.size(-1) == 7 && poses.numel() >= 7 &&
+                  poses.numel() < (1LL << 31),
+              "normalize_depth: poses must be [.., 7]");
+  TORCH_CHECK(disps.device() == poses.device(), "normalize_depth: tensors on different devices");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(disps.device());
+  auto disps_out = torch::empty_like(disps);
+  auto poses_out = torch::empty_like(poses);
+  auto s = torch::empty({3}, disps.options());
+  check_status(dpvo_normalize_depth(disps.data_ptr<float>(), (int)disps.numel(),
+                                    poses.data_ptr<float>(), (int)(poses.numel() / 7),
+                                    disps_out.data_ptr<float>(), poses_out.data_ptr<float>(),
+                                    s.data_ptr<float>(), current_stream()),
+               "cuda_ba.normalize_depth");
+  return {disps_out, poses_out, s};
+}
+
 // ---- tracker.hip: the small kernels of the tracker's frame path ----------------
 static int ring_dtype(const torch::Tensor& t, const char* name) {
   check_device(t, name);
@@ -1911,6 +2042,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[image uint8 [3, H, W], intrinsics float32 [4]]",
         py::arg("raw"), py::arg("calib"), py::arg("scale") = 1.0, py::arg("swap_rb") = false,
         py::arg("out") = py::none());
+  m.def("frame_flow_distance", &frame_flow_distance,
+        "mean clamped flow magnitude between every pair of frames (rgbd_utils.py:122-160), one "
+        "launch -> D float32 [N, N]",
+        py::arg("poses"), py::arg("disps"), py::arg("intrinsics"));
+  m.def("frame_graph", &frame_graph,
+        "the entries f D < max_flow as CSR (base.py:77-80) -> [rowptr i32 [N + 1], col i32 [nnz], "
+        "dist f32 [nnz]]",
+        py::arg("D"), py::arg("f") = 16.0, py::arg("max_flow") = 256.0);
+  m.def("rgbd_augment", &rgbd_augment,
+        "RGBDAugmentor.__call__ (augmentation.py) with the random draws given -> [images, disps, "
+        "intrinsics] of the crop",
+        py::arg("images"), py::arg("disps"), py::arg("intrinsics"), py::arg("crop_h"),
+        py::arg("crop_w"), py::arg("do_color"), py::arg("order"), py::arg("brightness"),
+        py::arg("contrast"), py::arg("saturation"), py::arg("hue"), py::arg("gray"),
+        py::arg("invert"), py::arg("scale"), py::arg("swap_rb"));
+  m.def("normalize_depth", &normalize_depth,
+        "s = 0.7 quantile(disps, 0.98) (base.py:171-173) -> [disps / s, poses with t s, "
+        "(s, lo, hi) f32 [3]]",
+        py::arg("disps"), py::arg("poses"));
   m.def("trajectory_ate", &trajectory_ate,
         "association, Sim(3) alignment and error statistics of two trajectories, one launch -> "
         "[stats f64[8], model f64[13], pairs i32[min(n, m), 2], status i32[1]]",

@@ -20,6 +20,7 @@
 
 #include "common.hpp"
 #include "lie_se3.hpp"
+#include "radix_select.hpp"
 
 namespace dpvo {
 namespace frontend {
@@ -49,15 +50,6 @@ __device__ __forceinline__ void store_pose(const G& g, float* __restrict__ p) {
 
 // ---- frame init ---------------------------------------------------------------
 constexpr int kFiT = 256;
-
-// order-preserving key of a float: a < b  <=>  key(a) < key(b) (-0 below +0)
-__device__ __forceinline__ uint32_t float_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 struct FrameInit {
   float* poses;
@@ -102,10 +94,7 @@ __device__ void seed_pose(const FrameInit& a, int n, int counter) {
 }
 
 __global__ void __launch_bounds__(kFiT) frame_init_kernel(FrameInit a) {
-  __shared__ int hist[256];
-  __shared__ int wtot[kFiT / kWave];
-  __shared__ uint32_t sel_prefix;
-  __shared__ int sel_rank;
+  __shared__ RadixSelectLds sel;
   __shared__ int any_nan;
   const int tid = threadIdx.x;
   const int n = a.n_dev ? *a.n_dev : a.n;
@@ -118,7 +107,6 @@ __global__ void __launch_bounds__(kFiT) frame_init_kernel(FrameInit a) {
   if (tid == 0) {
     a.tstamps[n] = counter;
     if (n > 1) seed_pose(a, n, counter);
-    sel_prefix = 0;
     any_nan = 0;
   }
   if (tid >= kWave && tid < kWave + 4)
@@ -131,41 +119,16 @@ __global__ void __launch_bounds__(kFiT) frame_init_kernel(FrameInit a) {
     const int f0 = max(n - 3, 0);
     const int count = (n - f0) * a.M * PP;
     const float* base = a.patches + (size_t)f0 * a.M * 3 * PP + 2 * PP;  // channel 2 of patch f0 M
-    if (tid == 0) sel_rank = (count - 1) / 2;
-    uint32_t prefix = 0;
-#pragma unroll 1
-    for (int pass = 0; pass < 4; pass++) {
-      const int shift = 24 - 8 * pass;
-      const uint32_t himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-      hist[tid] = 0;
-      __syncthreads();
-      bool nan = false;
-      for (int i = tid; i < count; i += kFiT) {
-        const int patch = i / PP, pix = i - patch * PP;
-        const float v = base[(size_t)patch * 3 * PP + pix];
-        nan |= v != v;
-        const uint32_t k = float_key(v);
-        if ((k & himask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
-      }
-      if (pass == 0 && nan) any_nan = 1;
-      __syncthreads();
-      // exclusive scan of the 256 bins, one per thread; the bin holding the rank is selected
-      const int c = hist[tid];
-      const int incl = wave_incl_sum(c);
-      if ((tid & 63) == 63) wtot[tid >> 6] = incl;
-      __syncthreads();
-      int excl = incl - c;
-      for (int w = 0; w < (tid >> 6); w++) excl += wtot[w];
-      const int rank = sel_rank;
-      __syncthreads();  // every thread has read sel_rank
-      if (c > 0 && rank >= excl && rank < excl + c) {
-        sel_prefix = prefix | ((uint32_t)tid << shift);
-        sel_rank = rank - excl;
-      }
-      __syncthreads();
-      prefix = sel_prefix;
-    }
-    s = any_nan ? __uint_as_float(0x7fc00000u) : key_float(prefix);
+    bool nan = false;
+    const uint32_t key = block_radix_select(count, (count - 1) / 2, [&](int i) {
+      const int patch = i / PP, pix = i - patch * PP;
+      const float v = base[(size_t)patch * 3 * PP + pix];
+      nan |= v != v;
+      return float_key(v);
+    }, sel);
+    if (nan) any_nan = 1;
+    __syncthreads();
+    s = any_nan ? __uint_as_float(0x7fc00000u) : key_float(key);
   }
 
   // ---- patches_[n] = patches, depth channel replaced by the median ----

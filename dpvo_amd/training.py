@@ -4,7 +4,8 @@
 kernels of csrc/train.hip (one launch each way, fp64 inside, fixed-order sums:
 two calls give identical bits; no host synchronisation).  ``sequence_loss``
 restates the loop of train.py:85-118 over a trajectory of ``VONet.forward``
-and ``train_step`` the step of train.py:77-125.  Data readers, the logger and
+and ``train_step`` the step of train.py:77-125.  The data readers that feed it
+are dpvo_amd.data_readers (scripts/train.py is the loop); the logger and
 checkpoint rotation are not part of this module.
 """
 from __future__ import annotations

@@ -759,6 +759,128 @@ int dpvo_trajectory_ate(const void* est_xyz, int est_dtype, const double* est_t,
                         int align, double* stats, double* model, int32_t* pairs, int32_t* status,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------ training data readers */
+
+/* The device half of dpvo/data_readers (base.py, rgbd_utils.py,
+   augmentation.py).  Every entry checks its arguments on the host before any
+   launch (null or misaligned pointers, non-positive sizes: DPVO_ERR_INVALID;
+   sizes past the stated capacity: DPVO_ERR_UNSUPPORTED; invalid first), runs on
+   `stream` without host synchronisation, and sums in a fixed order: two calls
+   give identical bits.  All arrays are device arrays, 4-byte aligned. */
+
+/* rgbd_utils.compute_distance_matrix_flow (rgbd_utils.py:122-160), one launch.
+   The reference calls pops.induced_flow, which does not exist; the flow is
+   defined through projective_ops.transform(.., valid=True) on P = 1 patches.
+     poses      float32 [N, 7] world-from-camera (tx ty tz qx qy qz qw), as the
+                dataset stores them
+     disps      float32 [N, h, w];  intrinsics float32 [N, 4] (fx fy cx cy)
+     D          float32 [N, N]
+   Inputs are fp32, all arithmetic is fp64, D is rounded to fp32 once.  With
+   G = inv(pose) and G_ab = G_b * inv(G_a) (quaternion product and action as
+   lietorch's, no renormalisation), the direction a -> b gives for every grid
+   point (x, y) of frame a
+     X0 = ((x - cx_a)/fx_a, (y - cy_a)/fy_a, 1);  d = disps[a, y, x]
+     X1 = R(G_ab) X0 + t(G_ab) d;  Z = X1.z
+     u = fx_b (X1.x / max(Z, 0.1)) + cx_b;  v = fy_b (X1.y / max(Z, 0.1)) + cy_b
+     mag = min(|(u - x, v - y)|, 100)      (a NaN flow counts as 100)
+     val = Z > 0.2                         (false for a NaN Z)
+   For i <= j the points of i -> j are summed first, then those of j -> i
+   (each lane of one wave takes points lane, lane + 64, .. in order, the 64
+   lanes are added in an xor tree); with n = 2 h w and k = sum val
+     D[i, j] = D[j, i] = (float)k / (float)n < 0.7f ? +inf : sum(mag val) / k
+   so D is symmetric bit for bit; the diagonal is computed like any entry.
+   Capacity: N <= 8192, h w <= 65536. */
+int dpvo_frame_flow_distance(const float* poses, const float* disps, const float* intrinsics, int N,
+                             int h, int w, float* D, void* stream);
+
+/* base.py:77-80 as CSR: row i holds the columns j, ascending, with
+   d = f * D[i, j] < max_flow (one fp32 product, as numpy's) and dist = d.
+   dpvo_frame_graph_count: rowptr int32 [N + 1] (a count per row, then the
+   project's workgroup scan; two launches), rowptr[N] = nnz.  The caller reads
+   nnz, allocates col int32 [nnz] and dist float32 [nnz] and calls
+   dpvo_frame_graph_fill with the same D, f and max_flow (one launch; nothing
+   is written at or past nnz).  f must be positive and finite, max_flow not
+   NaN.  Capacity: N <= 8192. */
+int dpvo_frame_graph_count(const float* D, int N, float f, float max_flow, int32_t* rowptr,
+                           void* stream);
+int dpvo_frame_graph_fill(const float* D, int N, float f, float max_flow, const int32_t* rowptr,
+                          int32_t* col, float* dist, int nnz, void* stream);
+
+/* The random draws of augmentation.py, made by the caller and passed by value:
+   the device work is a function of them alone. */
+typedef struct dpvo_augment_params {
+  int do_color;      /* 0: no colour map at all (the image values pass through) */
+  int order[4];      /* a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue */
+  float brightness, contrast, saturation;  /* factors, >= 0 (the reference draws [0.6, 1.4]) */
+  float hue;         /* shift in turns (the reference draws +-0.2 / 3.14) */
+  int gray, invert;  /* 0 / 1 */
+  double scale;      /* 1, or the resize factor (the reference draws 2^U(0, 0.5)) */
+  int swap_rb;       /* 0: plane 0 is red; 1: plane 2 is red (cv2.imread's order) */
+} dpvo_augment_params;
+
+/* RGBDAugmentor.__call__ (augmentation.py:24-66) with the draws in `params`.
+     images [N, 3, H, W] float32 in 0..255, disps [N, H, W], intrinsics [N, 4]
+     -> images_out [N, 3, ch, cw], disps_out [N, ch, cw], intrinsics_out [N, 4]
+   Colour (do_color), per pixel in fp32 without FMA contraction, (r, g, b) by
+   swap_rb, gray(r, g, b) = 0.299 r + 0.587 g + 0.114 b, clamp = to [0, 1]:
+     x = x / 255; then the four operations in `order`, each clamped:
+       brightness  x = clamp(x b)
+       contrast    x = clamp(c x + (1 - c) m), m = (float)(S / (N H W)) with S the
+                   fp64 sum of gray over all N frames as they stand when
+                   contrast's turn comes (a launch of its own: 256 workgroups,
+                   thread t of them takes pixels t, t + 65536, ..; xor tree in
+                   the wave, waves ascending, workgroups by the same tree)
+       saturation  x = clamp(s x + (1 - s) gray)
+       hue         maxc, minc, cr = maxc - minc; cr == 0: h = s = 0, else
+                   s = cr / maxc, (rc, gc, bc) = (maxc - (r, g, b)) / cr,
+                   h = maxc == r ? bc - gc : maxc == g ? 2 + rc - bc : 4 + gc - rc,
+                   h = fmod(h / 6 + 1, 1);  h = h + hue;  h = h - floor(h);
+                   h6 = 6 h, i = (int)floor(h6) % 6, f = h6 - floor(h6), v = maxc,
+                   p = v (1 - s), q = v (1 - f s), t = v (1 - (1 - f) s),
+                   (r, g, b) = (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q) by i;
+                   clamped
+     gray: r = g = b = gray(r, g, b);  invert: x = 1 - x;  x = x 255
+   The reference round-trips through PIL and quantises to uint8 between the
+   operations; this stays in fp32 and does not quantise.
+   Spatial: ht1 = (int)(scale H), wd1 = (int)(scale W), y0 = (ht1 - ch) / 2,
+   x0 = (wd1 - cw) / 2; only the crop window [y0, y0 + ch) x [x0, x0 + cw) of
+   the resized frame is computed.  scale == 1: no resampling, the window is
+   copied (with do_color = 0 bit for bit).  Otherwise, in fp32, for output pixel
+   (oy, ox) of the resized frame, sh = (float)H / ht1 (and sw likewise):
+     image   F.interpolate(mode='bicubic', align_corners=False): ry = sh (oy + 0.5)
+             - 0.5, iy = floor(ry), t = ry - iy, taps iy - 1 .. iy + 2 clamped to
+             [0, H - 1], weights of the cubic convolution with A = -0.75; rows
+             first, then the four row values; not clamped
+     depth   nearest: row min((int)floor(oy sh), H - 1)
+   intrinsics_out = (float)scale K - (0, 0, x0, y0), two fp32 roundings.
+   Colour then resampling goes through a scratch image in the workspace.
+   DPVO_ERR_INVALID also for: flags outside 0 / 1, an order that is not a
+   permutation, non-finite or negative factors, a non-finite hue, a scale that
+   is not finite and positive, and a crop that does not fit: ch > ht1 - 1 or
+   cw > wd1 - 1 when the frame is resized (augmentation.py:29-31 keeps the
+   resized frame larger than the crop), ch > H or cw > W at scale 1.
+   Capacity: H, W <= 16384, scale H and scale W <= 65536, 3 N H W < 2^31.
+   A short workspace: DPVO_ERR_WORKSPACE (8-byte aligned; 2048 bytes suffice
+   unless colour is followed by resampling, which needs the scratch image too). */
+size_t dpvo_rgbd_augment_workspace_bytes(int N, int H, int W);
+int dpvo_rgbd_augment(const float* images, const float* disps, const float* intrinsics, int N, int H,
+                      int W, int crop_h, int crop_w, const dpvo_augment_params* params,
+                      float* images_out, float* disps_out, float* intrinsics_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* base.py:171-173: s = 0.7 torch.quantile(disps, 0.98) over all n elements,
+   disps_out = disps / s, poses_out = poses with columns 0..2 times s (poses
+   float32 [nposes, 7]).  Two launches.  In fp32 as torch computes it:
+   pos = 0.98f (n - 1), lo = floor(pos), hi = ceil(pos), w = pos - lo; a and b
+   the values of sorted ranks lo and hi (exact, by the four-pass radix select
+   that dpvo_frame_init's median uses, one workgroup, once per rank);
+   q = w < 0.5 ? a + w (b - a) : b - (b - a)(1 - w) (torch's lerp); s = 0.7f q.
+   scale float32 [3] on the device = (s, a, b); any NaN among disps makes all
+   three NaN.  The outputs must not overlap the inputs.
+   Capacity: n <= 2^30, nposes <= 2^24. */
+int dpvo_normalize_depth(const float* disps, int n, const float* poses, int nposes, float* disps_out,
+                         float* poses_out, float* scale, void* stream);
+
 /* ------------------------------------------------------------------ tracker */
 
 /* The four small kernels of the tracker's frame path (dpvo_amd/dpvo.py), one
