@@ -17,17 +17,18 @@ namespace {
 torch::Tensor corr_impl(torch::Tensor fmap1, torch::Tensor* fmap2, int L, torch::Tensor coords,
                         torch::Tensor ii, torch::Tensor jj, int radius, const double* scales,
                         const c10::optional<torch::Tensor>& order, bool single, const char* what) {
-  check_device(fmap1, "fmap1");
-  check_device(coords, "coords");
+  const Entry a(what);
+  a.on_gpu(fmap1, "fmap1");
+  a.on_gpu(coords, "coords");
   TORCH_CHECK(L >= 1 && L <= 8, "one scale per pyramid level (1..8 levels)");
   TORCH_CHECK(fmap1.dim() == 5 && coords.dim() == 5 && coords.size(2) == 2 &&
                   coords.scalar_type() == torch::kFloat32,
               "corr: expected fmap1 [B,N1,C,H,W], fmap2 [B,N2,C,H2,W2], coords [B,M,2,H,W] float32");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(fmap1.device());
-  fmap1 = fmap1.contiguous();
-  coords = coords.contiguous();
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
+  int dt;
+  const void* f1 = a.in(fmap1, "fmap1", kF32 | kF16 | kF64, &dt);
+  const float* co = a.in<float>(coords, "coords");
+  const int64_t* ip = a.in<int64_t>(ii, "ii");
+  const int64_t* jp = a.in<int64_t>(jj, "jj");
   const int B = coords.size(0), M = coords.size(1), H = coords.size(3), W = coords.size(4);
   TORCH_CHECK(ii.numel() >= M && jj.numel() >= M, "ii/jj shorter than coords.size(1)");
   TORCH_CHECK(fmap1.size(3) == H && fmap1.size(4) == W, "fmap1 patch size != coords size");
@@ -37,96 +38,67 @@ torch::Tensor corr_impl(torch::Tensor fmap1, torch::Tensor* fmap2, int L, torch:
   bool nhwc = true;
   for (int l = 0; l < L; l++) {
     const torch::Tensor& f = fmap2[l];
-    check_device(f, "fmap2");
+    ptrs[l] = a.view(f, "fmap2", kF32 | kF16 | kF64);
     TORCH_CHECK(f.dim() == 5 && f.scalar_type() == fmap1.scalar_type(),
                 "fmap2 levels must be [B,N,C,H,W] of fmap1's dtype");
     nhwc = nhwc && f.permute({0, 1, 3, 4, 2}).is_contiguous() && f.size(2) > 1;
-    ptrs[l] = f.data_ptr();
     H2[l] = f.size(3);
     W2[l] = f.size(4);
     sc[l] = scales ? (float)scales[l] : 1.0f;
   }
   const int Dp = 2 * radius + 1, C = fmap1.size(2), N1 = fmap1.size(1), N2 = fmap2[0].size(1);
-  const float* co = coords.data_ptr<float>();
-  const int64_t *ip = ii.data_ptr<int64_t>(), *jp = jj.data_ptr<int64_t>();
+  const int32_t* ord = nullptr;
+  if (nhwc && order.has_value() && order->defined()) {
+    ord = a.buf<int32_t>(*order, "order");
+    TORCH_CHECK(order->numel() == M && B == 1, "order: contiguous int32 [E] (B == 1)");
+  }
+  const DeviceGuard guard(fmap1.device());
   torch::Tensor out;
   if (nhwc || !single)
     out = torch::empty({B, M, Dp, Dp, H, W, L}, fmap1.options().dtype(torch::kFloat32));
   if (nhwc) {
-    const int32_t* ord = nullptr;
-    if (order.has_value() && order->defined()) {
-      check_device(*order, "order");
-      TORCH_CHECK(order->scalar_type() == torch::kInt32 && order->is_contiguous() &&
-                      order->numel() == M && B == 1,
-                  "order: contiguous int32 [E] (B == 1)");
-      ord = order->data_ptr<int32_t>();
-    }
-    const int st = dpvo_corr_forward_levels_nhwc_ordered(
-        fmap1.data_ptr(), ptrs, H2, W2, sc, L, co, ip, jp, ord, B, M, C, H, W, N1, N2, radius,
-        dtype_code(fmap1), out.data_ptr<float>(), current_stream());
+    const int st = dpvo_corr_forward_levels_nhwc_ordered(f1, ptrs, H2, W2, sc, L, co, ip, jp, ord, B,
+                                                         M, C, H, W, N1, N2, radius, dt,
+                                                         out.data_ptr<float>(), current_stream());
     if (st != DPVO_ERR_UNSUPPORTED) {
       check_status(st, what);
       // forward: fp32 accumulation, returned in the fmap dtype as the reference does
       return single ? out.view({B, M, Dp, Dp, H, W}).to(fmap1.scalar_type()) : out;
     }
   }
-  for (int l = 0; l < L; l++) {
-    fmap2[l] = fmap2[l].contiguous();
-    ptrs[l] = fmap2[l].data_ptr();
-  }
+  for (int l = 0; l < L; l++) ptrs[l] = a.in(fmap2[l], "fmap2", kF32 | kF16 | kF64);
   if (single) {
     out = torch::empty({B, M, Dp, Dp, H, W}, fmap1.options());
-    check_status(dpvo_corr_forward(fmap1.data_ptr(), ptrs[0], co, ip, jp, B, M, C, H, W, N1, N2,
-                                   H2[0], W2[0], radius, dtype_code(fmap1), out.data_ptr(),
-                                   current_stream()),
+    check_status(dpvo_corr_forward(f1, ptrs[0], co, ip, jp, B, M, C, H, W, N1, N2, H2[0], W2[0],
+                                   radius, dt, out.data_ptr(), current_stream()),
                  what);
   } else {
-    check_status(dpvo_corr_forward_levels(fmap1.data_ptr(), ptrs, H2, W2, sc, L, co, ip, jp, B, M,
-                                          C, H, W, N1, N2, radius, dtype_code(fmap1),
-                                          out.data_ptr<float>(), current_stream()),
+    check_status(dpvo_corr_forward_levels(f1, ptrs, H2, W2, sc, L, co, ip, jp, B, M, C, H, W, N1,
+                                          N2, radius, dt, out.data_ptr<float>(), current_stream()),
                  what);
   }
   return out;
 }
 
-// The two frame insertions of a channels-last pyramid: src [C, H, W] (level-1
-// NCHW frame, fp32 / fp16), d[l] [C, H/s, W/s] views of src's dtype in
-// channels-last memory (one ring slot); slot_dev: the ring variant
-void insert_impl(torch::Tensor src, const std::vector<torch::Tensor>& d,
+// The two frame insertions of a channels-last pyramid (Entry::pyramid);
+// slot_dev: the ring variant
+void insert_impl(const char* fn, torch::Tensor src, const std::vector<torch::Tensor>& d,
                  const std::vector<int64_t>& scales, const char* name,
                  const torch::Tensor* slot_dev, int mem, const std::vector<int64_t>& slot_bytes) {
-  check_device(src, "src");
-  TORCH_CHECK(src.dim() == 3, "src must be [C, H, W]");
-  TORCH_CHECK(d.size() == scales.size() && !d.empty(), "one scale per ", name, " level");
-  TORCH_CHECK(src.scalar_type() == torch::kFloat32 || src.scalar_type() == torch::kFloat16,
-              "src must be float32 or float16");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
-  src = src.contiguous();
-  const int C = src.size(0), H = src.size(1), W = src.size(2), L = d.size();
-  std::vector<void*> ptrs;
-  std::vector<int> sc;
-  for (int l = 0; l < L; l++) {
-    check_device(d[l], name);
-    const int s = (int)scales[l];
-    TORCH_CHECK(d[l].scalar_type() == src.scalar_type() && d[l].dim() == 3 && d[l].size(0) == C &&
-                    s > 0 && d[l].size(1) == H / s && d[l].size(2) == W / s,
-                name, " level ", l, " must be [C, H/s, W/s] of src's dtype");
-    TORCH_CHECK(d[l].stride(0) == 1 && d[l].stride(2) == C &&
-                    d[l].stride(1) == (int64_t)C * d[l].size(2),
-                name, " level ", l, " must be channels-last");
-    ptrs.push_back(d[l].data_ptr());
-    sc.push_back(s);
-  }
-  if (slot_dev)
-    check_status(dpvo_feature_pyramid_insert_ring(src.data_ptr(), ptrs.data(), slot_bytes.data(),
-                                                  sc.data(), L, C, H, W, mem,
-                                                  slot_dev->data_ptr<int32_t>(), dtype_code(src),
-                                                  current_stream()),
-                 "cuda_corr.feature_pyramid_insert_ring");
+  const Entry a(fn);
+  const Pyramid p = a.pyramid(src, d, scales, name);
+  const int32_t* slot = slot_dev ? a.buf<int32_t>(*slot_dev, "slot_dev", 1) : nullptr;
+  const DeviceGuard guard(src.device());
+  const int L = p.dst.size();
+  if (slot)
+    check_status(dpvo_feature_pyramid_insert_ring(p.src, p.dst.data(), slot_bytes.data(),
+                                                  p.scales.data(), L, p.C, p.H, p.W, mem, slot,
+                                                  p.dtype, current_stream()),
+                 fn);
   else
-    check_status(dpvo_feature_pyramid_insert(src.data_ptr(), ptrs.data(), sc.data(), L, C, H, W,
-                                             dtype_code(src), current_stream()),
-                 "cuda_corr.feature_pyramid_insert");
+    check_status(dpvo_feature_pyramid_insert(p.src, p.dst.data(), p.scales.data(), L, p.C, p.H, p.W,
+                                             p.dtype, current_stream()),
+                 fn);
 }
 
 }  // namespace
@@ -153,33 +125,32 @@ torch::Tensor corr_forward_levels(torch::Tensor fmap1, std::vector<torch::Tensor
 // src [..., C, H, W] contiguous -> dst: same shape, channels-last memory
 // (dst.permute(..., H, W, C) contiguous), e.g. one frame of a pyramid level.
 void feature_to_nhwc(torch::Tensor src, torch::Tensor dst) {
-  check_device(src, "src");
-  check_device(dst, "dst");
+  const Entry a("cuda_corr.feature_to_nhwc");
+  a.on_gpu(src, "src");
+  a.on_gpu(dst, "dst");
   TORCH_CHECK(src.dim() >= 3 && src.sizes() == dst.sizes(), "src / dst shapes differ");
   TORCH_CHECK(src.scalar_type() == dst.scalar_type(), "src / dst dtypes differ");
   const int d = src.dim();
-  TORCH_CHECK(dst.movedim(d - 3, d - 1).is_contiguous(), "dst must be channels-last");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
-  src = src.contiguous();
+  int dt;
+  const void* sp = a.in(src, "src", kF32 | kF16 | kF64, &dt);
+  // dst is written through its channels-last view, which is the contiguous one
+  torch::Tensor dv = dst.movedim(d - 3, d - 1);
+  void* dp = a.buf(dv, "dst (channels-last)", kF32 | kF16 | kF64);
+  const DeviceGuard guard(src.device());
   const int C = src.size(d - 3), H = src.size(d - 2), W = src.size(d - 1);
   const int count = src.numel() / ((int64_t)C * H * W);
-  check_status(dpvo_feature_to_nhwc(src.data_ptr(), dst.data_ptr(), count, C, H, W,
-                                    dtype_code(src), current_stream()),
-               "cuda_corr.feature_to_nhwc");
+  check_status(dpvo_feature_to_nhwc(sp, dp, count, C, H, W, dt, current_stream()), a.fn());
 }
 
 void feature_pyramid_insert(torch::Tensor src, std::vector<torch::Tensor> dst,
                             std::vector<int64_t> scales) {
-  insert_impl(src, dst, scales, "dst", nullptr, 0, {});
+  insert_impl("cuda_corr.feature_pyramid_insert", src, dst, scales, "dst", nullptr, 0, {});
 }
 
 // ring variant: slot = *slot_dev % mem read on the device (graph-replayed
 // frames); rings[l] is the whole [B, mem, C, H/s, W/s] channels-last ring
 void feature_pyramid_insert_ring(torch::Tensor src, std::vector<torch::Tensor> rings,
                                  std::vector<int64_t> scales, torch::Tensor slot_dev) {
-  check_device(slot_dev, "slot_dev");
-  TORCH_CHECK(slot_dev.scalar_type() == torch::kInt32 && slot_dev.is_contiguous(),
-              "slot_dev must be a contiguous int32 device tensor");
   TORCH_CHECK(!rings.empty(), "one scale per ring level");
   const int mem = rings[0].dim() == 5 ? rings[0].size(1) : 0;
   std::vector<torch::Tensor> slot0;  // slot 0 of every ring
@@ -189,30 +160,35 @@ void feature_pyramid_insert_ring(torch::Tensor src, std::vector<torch::Tensor> r
     slot0.push_back(r[0][0]);
     slot_bytes.push_back(r.stride(1) * (int64_t)r.element_size());
   }
-  insert_impl(src, slot0, scales, "ring", &slot_dev, mem, slot_bytes);
+  insert_impl("cuda_corr.feature_pyramid_insert_ring", src, slot0, scales, "ring", &slot_dev, mem,
+              slot_bytes);
 }
 
 // correlation.cpp:40-48 -> correlation_kernel.cu:275-325
 std::vector<torch::Tensor> corr_backward(torch::Tensor fmap1, torch::Tensor fmap2,
                                          torch::Tensor coords, torch::Tensor ii, torch::Tensor jj,
                                          torch::Tensor corr_grad, int radius) {
-  check_device(fmap1, "fmap1");
-  check_device(corr_grad, "corr_grad");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(fmap1.device());
+  const Entry a("cuda_corr.backward");
+  a.on_gpu(fmap1, "fmap1");
+  a.on_gpu(fmap2, "fmap2");
+  a.on_gpu(coords, "coords");
+  a.on_gpu(corr_grad, "corr_grad");
+  const int64_t* ip = a.in<int64_t>(ii, "ii");
+  const int64_t* jp = a.in<int64_t>(jj, "jj");
+  const DeviceGuard guard(fmap1.device());
   const auto dtype = fmap1.scalar_type();
   // the atomic accumulation runs in fp32 for every input dtype
-  auto f1 = fmap1.to(torch::kFloat32).contiguous();
-  auto f2 = fmap2.to(torch::kFloat32).contiguous();
-  coords = coords.to(torch::kFloat32).contiguous();
-  auto g = corr_grad.to(torch::kFloat32).contiguous();
-  ii = idx64(ii, "ii");
-  jj = idx64(jj, "jj");
+  auto f1 = fmap1.to(torch::kFloat32), f2 = fmap2.to(torch::kFloat32);
+  auto g = corr_grad.to(torch::kFloat32);
+  coords = coords.to(torch::kFloat32);
+  const float* f1p = a.in<float>(f1, "fmap1");
+  const float* f2p = a.in<float>(f2, "fmap2");
+  const float* co = a.in<float>(coords, "coords");
+  const float* gp = a.in<float>(g, "corr_grad");
   const int B = coords.size(0), M = coords.size(1), H = coords.size(3), W = coords.size(4);
   auto g1 = torch::empty_like(f1);
   auto g2 = torch::empty_like(f2);
-  check_status(dpvo_corr_backward(f1.data_ptr(), f2.data_ptr(), coords.data_ptr<float>(),
-                                  ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(),
-                                  g.data_ptr<float>(), B, M, f1.size(2), H, W, f1.size(1),
+  check_status(dpvo_corr_backward(f1p, f2p, co, ip, jp, gp, B, M, f1.size(2), H, W, f1.size(1),
                                   f2.size(1), f2.size(3), f2.size(4), radius, DPVO_F32,
                                   g1.data_ptr(), g2.data_ptr(), current_stream()),
                "cuda_corr.backward");
@@ -223,19 +199,20 @@ std::vector<torch::Tensor> corr_backward(torch::Tensor fmap1, torch::Tensor fmap
 // fork's runtime patchify (clamp at the border), correlation_kernel.py:181-224
 template <bool CLAMP>
 std::vector<torch::Tensor> patchify_forward(torch::Tensor net, torch::Tensor coords, int radius) {
-  check_device(net, "net");
-  check_device(coords, "coords");
+  const Entry a("cuda_corr.patchify_forward");
+  a.on_gpu(coords, "coords");
+  int dt;
+  const void* np = a.in(net, "net", kF32 | kF16 | kF64, &dt);
   TORCH_CHECK(net.dim() == 4 && coords.dim() == 3 && coords.size(2) == 2,
               "patchify: expected net [B,C,H,W], coords [B,M,2]");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(net.device());
-  net = net.contiguous();
-  coords = coords.to(torch::kFloat32).contiguous();
+  const DeviceGuard guard(net.device());
+  coords = coords.to(torch::kFloat32);
+  const float* co = a.in<float>(coords, "coords");
   const int B = coords.size(0), M = coords.size(1), C = net.size(1), D = 2 * radius + 2;
   auto out = torch::empty({B, M, C, D, D}, net.options());
-  check_status(dpvo_patchify_forward(net.data_ptr(), coords.data_ptr<float>(), B, C, net.size(2),
-                                     net.size(3), M, radius, CLAMP ? 1 : 0, dtype_code(net),
-                                     out.data_ptr(), current_stream()),
-               "cuda_corr.patchify_forward");
+  check_status(dpvo_patchify_forward(np, co, B, C, net.size(2), net.size(3), M, radius,
+                                     CLAMP ? 1 : 0, dt, out.data_ptr(), current_stream()),
+               a.fn());
   return {out};
 }
 
@@ -243,18 +220,23 @@ std::vector<torch::Tensor> patchify_forward(torch::Tensor net, torch::Tensor coo
 template <bool CLAMP>
 std::vector<torch::Tensor> patchify_backward(torch::Tensor net, torch::Tensor coords,
                                              torch::Tensor gradient, int radius) {
-  check_device(net, "net");
-  check_device(gradient, "gradient");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(net.device());
-  coords = coords.to(torch::kFloat32).contiguous();
-  auto g = gradient.to(torch::kFloat32).contiguous();
+  const Entry a("cuda_corr.patchify_backward");
+  a.on_gpu(net, "net");
+  a.on_gpu(coords, "coords");
+  a.on_gpu(gradient, "gradient");
+  TORCH_CHECK(net.dim() == 4 && coords.dim() == 3 && coords.size(2) == 2,
+              "patchify: expected net [B,C,H,W], coords [B,M,2]");
+  const DeviceGuard guard(net.device());
+  coords = coords.to(torch::kFloat32);
+  auto g = gradient.to(torch::kFloat32);
+  const float* co = a.in<float>(coords, "coords");
+  const float* gp = a.in<float>(g, "gradient");
   const int B = coords.size(0), M = coords.size(1), C = net.size(1);
   auto out = torch::empty({net.size(0), C, net.size(2), net.size(3)},
                           net.options().dtype(torch::kFloat32));
-  check_status(dpvo_patchify_backward(g.data_ptr(), coords.data_ptr<float>(), B, C, net.size(2),
-                                      net.size(3), M, radius, CLAMP ? 1 : 0, DPVO_F32,
-                                      out.data_ptr(), current_stream()),
-               "cuda_corr.patchify_backward");
+  check_status(dpvo_patchify_backward(gp, co, B, C, net.size(2), net.size(3), M, radius,
+                                      CLAMP ? 1 : 0, DPVO_F32, out.data_ptr(), current_stream()),
+               a.fn());
   return {out.to(net.scalar_type())};
 }
 

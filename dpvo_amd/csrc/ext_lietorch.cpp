@@ -19,12 +19,6 @@ static void check_group(int g) {
 static int K_of(int g) { return g == 1 ? 3 : g == 3 ? 6 : 7; }
 static int N_of(int g) { return K_of(g) + 1; }
 
-static int lie_dtype(const torch::Tensor& t) {
-  TORCH_CHECK(t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kFloat64,
-              "lietorch_backends: float32 / float64 only (dispatch.h:41-42)");
-  return dtype_code(t);
-}
-
 // per-op row widths: what the kernels of lie.hip read from X, Y and grad
 static int x_dim(int g, int op) { return op == OP_EXP ? K_of(g) : N_of(g); }
 static int y_dim(int g, int op) {
@@ -45,8 +39,9 @@ static int grad_dim(int g, int op) {
   }
 }
 
-// every operand is [n, width] contiguous rows of X's dtype on X's device: the
-// kernels index n * width elements of each, so anything else is refused here
+// every operand is [n, width] contiguous rows of X's dtype (float32 / float64,
+// dispatch.h:41-42) on X's device: the kernels index n * width elements of
+// each, so anything else is refused here
 static void check_rows(const torch::Tensor& t, const char* name, const torch::Tensor& X, int64_t n,
                        int width) {
   TORCH_CHECK(t.dim() == 2, "lietorch_backends: ", name, " must be 2-D [n, ", width, "], got ",
@@ -56,20 +51,22 @@ static void check_rows(const torch::Tensor& t, const char* name, const torch::Te
   TORCH_CHECK(t.size(0) == n, "lietorch_backends: ", name, " has ", t.size(0), " rows, X has ", n);
   TORCH_CHECK(t.scalar_type() == X.scalar_type(), "lietorch_backends: ", name,
               " dtype mismatch with X");
-  TORCH_CHECK(t.is_contiguous(), "lietorch_backends: ", name, " must be contiguous");
-}
-static void check_on_device(const torch::Tensor& t, const char* name, const torch::Tensor& X) {
-  check_device(t, name);
-  TORCH_CHECK(t.device() == X.device(), "lietorch_backends: ", name, " is not on X's device");
 }
 
+struct Operands {
+  int n, dtype;
+  const void *X, *Y, *grad;  // Y / grad null where the op has none
+};
+
 // shapes and dtypes of all operands first, then where they live; `grad` is
-// null for a forward op.  Returns n.
-static int check_operands(int g, int op, const torch::Tensor& X, const torch::Tensor& Y,
-                          const torch::Tensor* grad) {
+// null for a forward op
+static Operands check_operands(int g, int op, const torch::Tensor& X, const torch::Tensor& Y,
+                               const torch::Tensor* grad) {
+  const Entry a("lietorch_backends");
   check_group(g);
   TORCH_CHECK(X.defined(), "lietorch_backends: X is undefined");
-  lie_dtype(X);
+  TORCH_CHECK(X.scalar_type() == torch::kFloat32 || X.scalar_type() == torch::kFloat64,
+              "lietorch_backends: float32 / float64 only (dispatch.h:41-42)");
   TORCH_CHECK(X.dim() == 2, "lietorch_backends: X must be 2-D [n, ", x_dim(g, op), "], got ",
               X.dim(), "-D");
   const int64_t n = X.size(0);
@@ -83,31 +80,31 @@ static int check_operands(int g, int op, const torch::Tensor& X, const torch::Te
     TORCH_CHECK(grad->defined(), "lietorch_backends: grad is undefined");
     check_rows(*grad, "grad", X, n, grad_dim(g, op));
   }
-  check_on_device(X, "X", X);
-  if (yd > 0) check_on_device(Y, "Y", X);
-  if (grad) check_on_device(*grad, "grad", X);
-  return (int)n;
+  Operands o = {(int)n, 0, nullptr, nullptr, nullptr};
+  o.X = a.buf(X, "X", kF32 | kF64, &o.dtype);
+  if (yd > 0) o.Y = a.buf(Y, "Y", kF32 | kF64);
+  if (grad) o.grad = a.buf(*grad, "grad", kF32 | kF64);
+  if (yd > 0) a.same_device({X, Y});
+  if (grad) a.same_device({X, *grad});
+  return o;
 }
 
 static torch::Tensor fwd(int g, int op, torch::Tensor X, torch::Tensor Y, int out_dim) {
-  const int n = check_operands(g, op, X, Y, nullptr);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
-  auto out = torch::empty({n, out_dim}, X.options());
-  check_status(dpvo_lie_forward(g, op, lie_dtype(X), n, X.data_ptr(),
-                                Y.defined() ? Y.data_ptr() : nullptr, out.data_ptr(),
-                                current_stream()),
+  const Operands o = check_operands(g, op, X, Y, nullptr);
+  const DeviceGuard guard(X.device());
+  auto out = torch::empty({o.n, out_dim}, X.options());
+  check_status(dpvo_lie_forward(g, op, o.dtype, o.n, o.X, o.Y, out.data_ptr(), current_stream()),
                "lietorch_backends forward");
   return out;
 }
 
 static std::vector<torch::Tensor> bwd(int g, int op, torch::Tensor grad, torch::Tensor X,
                                       torch::Tensor Y, int d0, int d1) {
-  const int n = check_operands(g, op, X, Y, &grad);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(X.device());
-  auto o0 = torch::empty({n, d0}, X.options());
-  auto o1 = d1 > 0 ? torch::empty({n, d1}, X.options()) : torch::Tensor();
-  check_status(dpvo_lie_backward(g, op, lie_dtype(X), n, grad.data_ptr(), X.data_ptr(),
-                                 Y.defined() ? Y.data_ptr() : nullptr, o0.data_ptr(),
+  const Operands o = check_operands(g, op, X, Y, &grad);
+  const DeviceGuard guard(X.device());
+  auto o0 = torch::empty({o.n, d0}, X.options());
+  auto o1 = d1 > 0 ? torch::empty({o.n, d1}, X.options()) : torch::Tensor();
+  check_status(dpvo_lie_backward(g, op, o.dtype, o.n, o.grad, o.X, o.Y, o0.data_ptr(),
                                  d1 > 0 ? o1.data_ptr() : nullptr, current_stream()),
                "lietorch_backends backward");
   if (d1 > 0) return {o0, o1};

@@ -9,35 +9,26 @@
 
 using namespace dpvo_ext;
 
-static int wdtype_code(int64_t code) {
-  TORCH_CHECK(code == DPVO_F32 || code == DPVO_F16, "dpvo_update: weights are float32 or float16");
-  return (int)code;
+static int64_t packed_bytes(int64_t K0, int64_t wdtype) {
+  const int wd = Entry("dpvo_update.packed_bytes").wdtype_code(wdtype);
+  return (int64_t)dpvo_update_packed_bytes((int)K0, wd);
 }
 
-static int64_t packed_bytes(int64_t K0, int64_t wdtype) {
-  return (int64_t)dpvo_update_packed_bytes((int)K0, wdtype_code(wdtype));
+// element counts of Update's 50 parameter tensors in state_dict order
+static std::function<int64_t(size_t)> param_numel(int64_t K0) {
+  return [K0](size_t i) -> int64_t {
+    return (i % 2 == 0 && i != 8 && i != 22 && i != 30 && i != 42)
+               ? (i == 38 ? 384 * K0 : (i >= 46 ? 2 * 384 : 384 * 384))
+               : (i == 47 || i == 49 ? 2 : 384);
+  };
 }
 
 // 50 CPU float32 tensors in state_dict order -> packed host blob (uint8)
 static torch::Tensor pack_weights(std::vector<torch::Tensor> tensors, int64_t K0, int64_t wdtype) {
-  TORCH_CHECK(tensors.size() == 50, "dpvo_update.pack_weights: expected the 50 parameter tensors of "
-                                    "Update, got ", tensors.size());
+  const Entry a("dpvo_update.pack_weights");
   TORCH_CHECK(K0 >= 1 && K0 <= INT_MAX, "dpvo_update.pack_weights: bad corr_dim ", K0);
-  std::vector<const float*> ptrs;
-  for (size_t i = 0; i < tensors.size(); i++) {
-    auto& t = tensors[i];
-    TORCH_CHECK(!t.is_cuda(), "dpvo_update.pack_weights: tensor ", i, " must be a CPU tensor");
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32, "dpvo_update.pack_weights: tensor ", i,
-                " must be float32");
-    t = t.contiguous();
-    const int64_t want = (i % 2 == 0 && i != 8 && i != 22 && i != 30 && i != 42)
-                             ? (i == 38 ? 384 * K0 : (i >= 46 ? 2 * 384 : 384 * 384))
-                             : (i == 47 || i == 49 ? 2 : 384);
-    TORCH_CHECK(t.numel() == want, "dpvo_update.pack_weights: tensor ", i, " has ", t.numel(),
-                " elements, expected ", want);
-    ptrs.push_back(t.data_ptr<float>());
-  }
-  const int wd = wdtype_code(wdtype);
+  const auto ptrs = a.host_params(tensors, 50, param_numel(K0));
+  const int wd = a.wdtype_code(wdtype);
   const size_t bytes = dpvo_update_packed_bytes((int)K0, wd);
   auto blob = torch::empty({(int64_t)bytes}, torch::dtype(torch::kUInt8));
   check_status(dpvo_update_pack_weights(ptrs.data(), 50, 384, (int)K0, wd, blob.data_ptr(), bytes),
@@ -49,133 +40,75 @@ static int64_t workspace_bytes(int64_t E, int64_t K0) {
   return (int64_t)dpvo_update_workspace_bytes((int)E, (int)K0);
 }
 
-static void check_ws(const torch::Tensor& ws, const torch::Tensor& like) {
-  check_device(ws, "workspace");
-  TORCH_CHECK(ws.device() == like.device(), "dpvo_update: workspace is on another device");
-  TORCH_CHECK(ws.scalar_type() == torch::kUInt8 && ws.is_contiguous(),
-              "dpvo_update: workspace must be a contiguous uint8 tensor");
-}
-
 static void plan(torch::Tensor gk, torch::Tensor gij, torch::Tensor workspace) {
-  gk = idx64(gk, "gk");
-  gij = idx64(gij, "gij");
+  const Entry a("dpvo_update.plan");
+  const int64_t* kp = a.in<int64_t>(gk, "gk");
+  const int64_t* jp = a.in<int64_t>(gij, "gij");
   TORCH_CHECK(gk.dim() == 1 && gij.dim() == 1 && gk.numel() == gij.numel(),
               "dpvo_update.plan: gk and gij must be 1-D of one length");
-  TORCH_CHECK(gij.device() == gk.device(), "dpvo_update.plan: gij is not on gk's device");
+  a.same_device({gk, gij});
   TORCH_CHECK(gk.numel() <= INT_MAX, "dpvo_update.plan: too many edges");
-  check_ws(workspace, gk);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(gk.device());
-  check_status(dpvo_update_plan(gk.data_ptr<int64_t>(), gij.data_ptr<int64_t>(), (int)gk.numel(),
-                                workspace.data_ptr(), (size_t)workspace.numel(), current_stream()),
+  void* ws = a.bytes(workspace, "workspace", gk.device());
+  const DeviceGuard guard(gk.device());
+  check_status(dpvo_update_plan(kp, jp, (int)gk.numel(), ws, (size_t)workspace.numel(),
+                                current_stream()),
                "dpvo_update_plan");
+}
+
+// t: contiguous [E, cols] of dtype `accept` on like's device
+static void* rows(const Entry& a, const torch::Tensor& t, const torch::Tensor& like, int64_t E,
+                  int64_t cols, unsigned accept, const char* name) {
+  void* p = a.buf(t, name, accept);
+  TORCH_CHECK(t.device() == like.device() && t.numel() == E * cols, a.fn(), ": ", name,
+              " must be [E, ", cols, "] on the inputs' device");
+  return p;
 }
 
 static void forward(torch::Tensor blob, int64_t wdtype, torch::Tensor net, torch::Tensor inp,
                     torch::Tensor corr, torch::Tensor ix, torch::Tensor jx, torch::Tensor workspace,
                     torch::Tensor net_out, torch::Tensor d, torch::Tensor w) {
-  check_device(net, "net");
-  const int wd = wdtype_code(wdtype);
-  const int io = dtype_code(net);
-  TORCH_CHECK(io == DPVO_F32 || (io == DPVO_F16 && wd == DPVO_F16),
+  const Entry a("dpvo_update.forward");
+  const int wd = a.wdtype_code(wdtype);
+  int io;
+  const void* np = a.buf(net, "net", kF32 | kF16, &io);
+  TORCH_CHECK(io == DPVO_F32 || wd == DPVO_F16,
               "dpvo_update.forward: net/inp/corr are float32, or float16 with float16 weights");
   TORCH_CHECK(net.dim() == 2 && net.size(1) == 384, "dpvo_update.forward: net must be [E, 384]");
   const int64_t E = net.size(0);
   TORCH_CHECK(E <= INT_MAX, "dpvo_update.forward: too many edges");
+  a.on_gpu(corr, "corr");
   TORCH_CHECK(corr.dim() == 2 && corr.size(0) == E && corr.size(1) >= 1,
               "dpvo_update.forward: corr must be [E, corr_dim]");
   const int64_t K0 = corr.size(1);
-  const torch::Tensor* same[] = {&inp, &corr, &net_out};
-  const char* names[] = {"inp", "corr", "net_out"};
-  for (int i = 0; i < 3; i++) {
-    check_device(*same[i], names[i]);
-    TORCH_CHECK(same[i]->device() == net.device(), "dpvo_update.forward: ", names[i],
-                " is not on net's device");
-    TORCH_CHECK(same[i]->scalar_type() == net.scalar_type(), "dpvo_update.forward: ", names[i],
-                " dtype differs from net's");
-    TORCH_CHECK(same[i]->is_contiguous(), "dpvo_update.forward: ", names[i], " must be contiguous");
-  }
-  TORCH_CHECK(net.is_contiguous(), "dpvo_update.forward: net must be contiguous");
-  TORCH_CHECK(inp.sizes() == net.sizes() && net_out.sizes() == net.sizes(),
-              "dpvo_update.forward: inp and net_out must have net's shape");
-  ix = idx64(ix, "ix");
-  jx = idx64(jx, "jx");
+  const unsigned same = io == DPVO_F32 ? kF32 : kF16;
+  const void* ip = rows(a, inp, net, E, 384, same, "inp");
+  const void* cp = rows(a, corr, net, E, K0, same, "corr");
+  void* op = rows(a, net_out, net, E, 384, same, "net_out");
+  float* dp = (float*)rows(a, d, net, E, 2, kF32, "d");
+  float* wp = (float*)rows(a, w, net, E, 2, kF32, "w");
+  const int64_t* ixp = a.in<int64_t>(ix, "ix");
+  const int64_t* jxp = a.in<int64_t>(jx, "jx");
   TORCH_CHECK(ix.numel() == E && jx.numel() == E, "dpvo_update.forward: ix, jx must have E elements");
-  TORCH_CHECK(ix.device() == net.device() && jx.device() == net.device(),
-              "dpvo_update.forward: ix / jx are not on net's device");
-  const torch::Tensor* outs[] = {&d, &w};
-  for (auto* o : outs) {
-    check_device(*o, "d / w");
-    TORCH_CHECK(o->device() == net.device() && o->scalar_type() == torch::kFloat32 &&
-                    o->is_contiguous() && o->numel() == 2 * E,
-                "dpvo_update.forward: d and w must be contiguous float32 [E, 2] on net's device");
-  }
-  check_device(blob, "blob");
-  TORCH_CHECK(blob.device() == net.device() && blob.scalar_type() == torch::kUInt8 &&
-                  blob.is_contiguous(),
-              "dpvo_update.forward: blob must be a contiguous uint8 tensor on net's device");
-  TORCH_CHECK((size_t)blob.numel() == dpvo_update_packed_bytes((int)K0, wd),
-              "dpvo_update.forward: blob was not packed for corr_dim ", K0, " and this weight dtype");
-  check_ws(workspace, net);
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(net.device());
-  check_status(dpvo_update_forward(blob.data_ptr(), wd, net.data_ptr(), inp.data_ptr(),
-                                   corr.data_ptr(), ix.data_ptr<int64_t>(), jx.data_ptr<int64_t>(),
-                                   (int)E, 384, (int)K0, io, workspace.data_ptr(),
-                                   (size_t)workspace.numel(), net_out.data_ptr(),
-                                   d.data_ptr<float>(), w.data_ptr<float>(), current_stream()),
+  a.same_device({net, ix, jx});
+  const void* bp = a.bytes(blob, "blob (packed for this corr_dim and weight dtype)", net.device(),
+                           dpvo_update_packed_bytes((int)K0, wd), true);
+  void* ws = a.bytes(workspace, "workspace", net.device());
+  const DeviceGuard guard(net.device());
+  check_status(dpvo_update_forward(bp, wd, np, ip, cp, ixp, jxp, (int)E, 384, (int)K0, io, ws,
+                                   (size_t)workspace.numel(), op, dp, wp, current_stream()),
                "dpvo_update_forward");
 }
 
 // --- the training surface ------------------------------------------------------------
-static int64_t param_numel(size_t i, int64_t K0) {
-  return (i % 2 == 0 && i != 8 && i != 22 && i != 30 && i != 42)
-             ? (i == 38 ? 384 * K0 : (i >= 46 ? 2 * 384 : 384 * 384))
-             : (i == 47 || i == 49 ? 2 : 384);
-}
-
-// 50 contiguous float32 device tensors of Update's shapes -> their data pointers
-static std::vector<float*> device_params(const std::vector<torch::Tensor>& ts, int64_t K0,
-                                         const torch::Device& dev, const char* what) {
-  TORCH_CHECK(ts.size() == 50, "dpvo_update: ", what, ": expected 50 tensors, got ", ts.size());
-  std::vector<float*> ptrs;
-  for (size_t i = 0; i < ts.size(); i++) {
-    const auto& t = ts[i];
-    check_device(t, what);
-    TORCH_CHECK(t.device() == dev, "dpvo_update: ", what, " ", i, " is on another device");
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "dpvo_update: ", what, " ",
-                i, " must be contiguous float32");
-    TORCH_CHECK(t.numel() == param_numel(i, K0), "dpvo_update: ", what, " ", i, " has ", t.numel(),
-                " elements, expected ", param_numel(i, K0));
-    ptrs.push_back(t.data_ptr<float>());
-  }
-  return ptrs;
-}
-
-static void check_bytes(const torch::Tensor& t, const torch::Tensor& like, const char* name) {
-  check_device(t, name);
-  TORCH_CHECK(t.device() == like.device() && t.scalar_type() == torch::kUInt8 && t.is_contiguous(),
-              "dpvo_update: ", name, " must be a contiguous uint8 tensor on the inputs' device");
-}
-
-static void check_rows(const torch::Tensor& t, const torch::Tensor& like, int64_t E, int64_t cols,
-                       const char* name) {
-  check_device(t, name);
-  TORCH_CHECK(t.device() == like.device() && t.scalar_type() == torch::kFloat32 &&
-                  t.is_contiguous() && t.numel() == E * cols,
-              "dpvo_update: ", name, " must be contiguous float32 [E, ", cols,
-              "] on the inputs' device");
-}
-
 static void pack_weights_device(std::vector<torch::Tensor> params, int64_t K0, int64_t wdtype,
                                 torch::Tensor blob) {
+  const Entry a("dpvo_update.pack_weights_device");
   TORCH_CHECK(K0 >= 1 && K0 <= INT_MAX, "dpvo_update.pack_weights_device: bad corr_dim ", K0);
-  check_device(blob, "blob");
-  const auto ptrs = device_params(params, K0, blob.device(), "params");
-  TORCH_CHECK(blob.scalar_type() == torch::kUInt8 && blob.is_contiguous(),
-              "dpvo_update.pack_weights_device: blob must be a contiguous uint8 tensor");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(blob.device());
-  check_status(dpvo_update_pack_weights_device(ptrs.data(), 384, (int)K0, wdtype_code(wdtype),
-                                               blob.data_ptr(), (size_t)blob.numel(),
-                                               current_stream()),
+  void* bp = a.bytes(blob, "blob", blob.device());
+  const auto ptrs = a.device_params(params, 50, param_numel(K0), blob.device(), "params");
+  const DeviceGuard guard(blob.device());
+  check_status(dpvo_update_pack_weights_device(ptrs.data(), 384, (int)K0, a.wdtype_code(wdtype),
+                                               bp, (size_t)blob.numel(), current_stream()),
                "dpvo_update_pack_weights_device");
 }
 
@@ -191,49 +124,45 @@ static void forward_train(torch::Tensor blob, torch::Tensor net, torch::Tensor i
                           torch::Tensor corr, torch::Tensor ix, torch::Tensor jx,
                           torch::Tensor workspace, torch::Tensor saved, torch::Tensor net_out,
                           torch::Tensor d, torch::Tensor w) {
-  check_device(net, "net");
-  TORCH_CHECK(net.scalar_type() == torch::kFloat32, "dpvo_update.forward_train: float32 only");
-  TORCH_CHECK(net.dim() == 2 && net.size(1) == 384 && net.is_contiguous(),
+  const Entry a("dpvo_update.forward_train");
+  const void* np = a.buf<float>(net, "net");
+  TORCH_CHECK(net.dim() == 2 && net.size(1) == 384,
               "dpvo_update.forward_train: net must be contiguous [E, 384]");
   const int64_t E = net.size(0);
   TORCH_CHECK(E <= INT_MAX, "dpvo_update.forward_train: too many edges");
+  a.on_gpu(corr, "corr");
   TORCH_CHECK(corr.dim() == 2 && corr.size(0) == E && corr.size(1) >= 1,
               "dpvo_update.forward_train: corr must be [E, corr_dim]");
   const int64_t K0 = corr.size(1);
-  check_rows(inp, net, E, 384, "inp");
-  check_rows(corr, net, E, K0, "corr");
-  check_rows(net_out, net, E, 384, "net_out");
-  check_rows(d, net, E, 2, "d");
-  check_rows(w, net, E, 2, "w");
-  ix = idx64(ix, "ix");
-  jx = idx64(jx, "jx");
-  TORCH_CHECK(ix.numel() == E && jx.numel() == E && ix.device() == net.device() &&
-                  jx.device() == net.device(),
-              "dpvo_update.forward_train: ix, jx must have E elements on net's device");
-  check_bytes(blob, net, "blob");
-  TORCH_CHECK((size_t)blob.numel() == dpvo_update_packed_bytes((int)K0, DPVO_F32),
-              "dpvo_update.forward_train: blob was not packed as float32 for corr_dim ", K0);
-  check_ws(workspace, net);
-  check_bytes(saved, net, "saved");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(net.device());
-  check_status(dpvo_update_forward_train(
-                   blob.data_ptr(), DPVO_F32, net.data_ptr(), inp.data_ptr(), corr.data_ptr(),
-                   ix.data_ptr<int64_t>(), jx.data_ptr<int64_t>(), (int)E, 384, (int)K0, DPVO_F32,
-                   workspace.data_ptr(), (size_t)workspace.numel(), saved.data_ptr(),
-                   (size_t)saved.numel(), net_out.data_ptr(), d.data_ptr<float>(),
-                   w.data_ptr<float>(), current_stream()),
+  const void* ip = rows(a, inp, net, E, 384, kF32, "inp");
+  const void* cp = rows(a, corr, net, E, K0, kF32, "corr");
+  void* op = rows(a, net_out, net, E, 384, kF32, "net_out");
+  float* dp = (float*)rows(a, d, net, E, 2, kF32, "d");
+  float* wp = (float*)rows(a, w, net, E, 2, kF32, "w");
+  const int64_t* ixp = a.in<int64_t>(ix, "ix");
+  const int64_t* jxp = a.in<int64_t>(jx, "jx");
+  TORCH_CHECK(ix.numel() == E && jx.numel() == E,
+              "dpvo_update.forward_train: ix, jx must have E elements");
+  a.same_device({net, ix, jx});
+  const void* bp = a.bytes(blob, "blob (packed as float32 for this corr_dim)", net.device(),
+                           dpvo_update_packed_bytes((int)K0, DPVO_F32), true);
+  void* ws = a.bytes(workspace, "workspace", net.device());
+  void* sv = a.bytes(saved, "saved", net.device());
+  const DeviceGuard guard(net.device());
+  check_status(dpvo_update_forward_train(bp, DPVO_F32, np, ip, cp, ixp, jxp, (int)E, 384, (int)K0,
+                                         DPVO_F32, ws, (size_t)workspace.numel(), sv,
+                                         (size_t)saved.numel(), op, dp, wp, current_stream()),
                "dpvo_update_forward_train");
 }
 
 // uint8 [6, E, 384]
 static torch::Tensor relu_masks(torch::Tensor saved, int64_t E, int64_t K0) {
-  check_device(saved, "saved");
-  TORCH_CHECK(saved.scalar_type() == torch::kUInt8 && saved.is_contiguous(),
-              "dpvo_update.relu_masks: saved must be a contiguous uint8 tensor");
+  const Entry a("dpvo_update.relu_masks");
+  const void* sv = a.bytes(saved, "saved", saved.device());
   TORCH_CHECK(E >= 0 && E <= INT_MAX && K0 >= 1 && K0 <= INT_MAX, "dpvo_update.relu_masks: bad sizes");
+  const DeviceGuard guard(saved.device());
   auto out = torch::empty({6, E, 384}, torch::dtype(torch::kUInt8).device(saved.device()));
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(saved.device());
-  check_status(dpvo_update_saved_relu_masks(saved.data_ptr(), (size_t)saved.numel(), (int)E, (int)K0,
+  check_status(dpvo_update_saved_relu_masks(sv, (size_t)saved.numel(), (int)E, (int)K0,
                                             out.data_ptr<uint8_t>(), current_stream()),
                "dpvo_update_saved_relu_masks");
   return out;
@@ -247,30 +176,32 @@ static void backward(std::vector<torch::Tensor> params, torch::Tensor saved, tor
                      c10::optional<torch::Tensor> g_net, c10::optional<torch::Tensor> g_inp,
                      c10::optional<torch::Tensor> g_corr, std::vector<torch::Tensor> grads,
                      torch::Tensor workspace) {
-  ix = idx64(ix, "ix");
-  jx = idx64(jx, "jx");
+  const Entry a("dpvo_update.backward");
+  const int64_t* ixp = a.in<int64_t>(ix, "ix");
+  const int64_t* jxp = a.in<int64_t>(jx, "jx");
   const int64_t E = ix.numel();
   TORCH_CHECK(jx.numel() == E && jx.device() == ix.device() && E <= INT_MAX,
               "dpvo_update.backward: ix, jx must have E elements on one device");
   TORCH_CHECK(K0 >= 1 && K0 <= INT_MAX, "dpvo_update.backward: bad corr_dim ", K0);
-  const auto pp = device_params(params, K0, ix.device(), "params");
+  const auto pp = a.device_params(params, 50, param_numel(K0), ix.device(), "params");
   std::vector<float*> gp;
-  if (!grads.empty()) gp = device_params(grads, K0, ix.device(), "grads");
-  check_bytes(saved, ix, "saved");
-  check_bytes(workspace, ix, "workspace");
+  if (!grads.empty()) gp = a.device_params(grads, 50, param_numel(K0), ix.device(), "grads");
+  const void* sv = a.bytes(saved, "saved", ix.device());
+  void* ws = a.bytes(workspace, "workspace", ix.device());
   auto opt = [&](const c10::optional<torch::Tensor>& t, int64_t cols, const char* name) -> float* {
-    if (!t.has_value()) return nullptr;
-    check_rows(*t, ix, E, cols, name);
-    return t->data_ptr<float>();
+    return t.has_value() ? (float*)rows(a, *t, ix, E, cols, kF32, name) : nullptr;
   };
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(ix.device());
-  check_status(dpvo_update_backward(
-                   pp.data(), 384, (int)K0, saved.data_ptr(), (size_t)saved.numel(),
-                   ix.data_ptr<int64_t>(), jx.data_ptr<int64_t>(), (int)E,
-                   opt(g_net_out, 384, "g_net_out"), opt(g_d, 2, "g_d"), opt(g_w, 2, "g_w"),
-                   opt(g_net, 384, "g_net"), opt(g_inp, 384, "g_inp"), opt(g_corr, K0, "g_corr"),
-                   gp.empty() ? nullptr : gp.data(), workspace.data_ptr(),
-                   (size_t)workspace.numel(), current_stream()),
+  float* gno = opt(g_net_out, 384, "g_net_out");
+  float* gd = opt(g_d, 2, "g_d");
+  float* gw = opt(g_w, 2, "g_w");
+  float* gn = opt(g_net, 384, "g_net");
+  float* gi = opt(g_inp, 384, "g_inp");
+  float* gc = opt(g_corr, K0, "g_corr");
+  const DeviceGuard guard(ix.device());
+  check_status(dpvo_update_backward(pp.data(), 384, (int)K0, sv, (size_t)saved.numel(), ixp, jxp,
+                                    (int)E, gno, gd, gw, gn, gi, gc,
+                                    gp.empty() ? nullptr : gp.data(), ws,
+                                    (size_t)workspace.numel(), current_stream()),
                "dpvo_update_backward");
 }
 

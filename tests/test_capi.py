@@ -499,3 +499,167 @@ def test_cpu_tensors_are_rejected_loudly():
     ii = torch.zeros(1, dtype=torch.long)
     with pytest.raises(RuntimeError, match="GPU"):
         corr.forward(f1, f2, co, ii, ii, 3)
+
+
+def _cpu_calls():
+    """module -> {entry: call with CPU tensors of the right dtype and shape in
+    every tensor slot}: 4 poses, 6 patches of 3 x 3, 8 edges, window (1, 4)."""
+    import torch
+
+    def f(*s):
+        return torch.zeros(*s)
+
+    def d(*s):
+        return torch.zeros(*s, dtype=torch.float64)
+
+    def l(*s):
+        return torch.zeros(*s, dtype=torch.long)
+
+    def i(*s):
+        return torch.zeros(*s, dtype=torch.int32)
+
+    def u8(*s):
+        return torch.zeros(*s, dtype=torch.uint8)
+
+    poses, patches, intr = f(4, 7), f(6, 3, 3, 3), f(4, 4)
+    ii, jj, kk = l(8), l(8), l(8)
+    tgt, wgt, lm = f(8, 2), f(8, 2), f(1)
+    edge = (poses, patches, intr, ii, jj, kk)
+    ba = (poses, patches, intr, tgt, wgt, lm, ii, jj, kk)
+    ws, t0_dev = u8(64), i(1)
+    src, dst = f(8, 8, 8), [f(8, 8, 8).permute(2, 0, 1), f(4, 4, 8).permute(2, 0, 1)]
+    # the patch-graph store: max_edges 16, DIM 16, counts of 3 words
+    live = [l(16), l(16), l(16), f(16, 16)]
+    act, back = live + [f(16, 2), f(16, 2)], [l(16), l(16), l(16), f(16, 16), f(16, 2), f(16, 2)]
+    inac = [l(16), l(16), l(16), f(16, 2), f(16, 2)]
+    counts, pos, ix, st, kf, mag = i(3), i(16), l(6), i(1), i(2), f(2)
+    coords = f(8, 3, 3, 2)
+    disps, images = f(4, 6, 8), f(4, 3, 6, 8)
+    kps = f(5, 2)
+    cuda_ba = {
+        "forward": lambda m: m.forward(*ba, 1, 1, 4, 2, False),
+        "forward_dx": lambda m: m.forward_dx(*ba, 1, 1, 4, 2, False),
+        "forward_marks": lambda m: m.forward_marks(*ba, 1, 1, 4, 2, False),
+        "forward_planned": lambda m: m.forward_planned(ws, *ba, 1, 4, 2),
+        "forward_planned_dev": lambda m: m.forward_planned_dev(ws, *ba, t0_dev, 3, 2),
+        "reproject": lambda m: m.reproject(*edge),
+        "reproject_ordered": lambda m: m.reproject_ordered(*edge, 4),
+        "reproject_ordered_plan": lambda m: m.reproject_ordered_plan(*edge, 4, 1, 4),
+        "reproject_ordered_plan_dev": lambda m: m.reproject_ordered_plan_dev(*edge, 4, t0_dev, 3),
+        "reproject_ordered_plan_insert": lambda m: m.reproject_ordered_plan_insert(
+            *edge, 4, 1, 4, src, dst, [1, 2]),
+        "neighbors": lambda m: m.neighbors(ii, jj),
+        "pgo_residual": lambda m: m.pgo_residual(f(5, 7), f(3, 8), l(3), l(3), True),
+        "ransac_umeyama": lambda m: m.ransac_umeyama(f(20, 3), f(20, 3), i(2, 3), 0.1, 100),
+        "setup": lambda m: m.setup(ii, jj, kk, 6, 1, 4),
+        "plan": lambda m: m.plan(ii, jj, kk, 6, 4, 1, 4),
+        "build_schur": lambda m: m.build_schur(ws, *ba, 1, 4),
+        "solve_update": lambda m: m.solve_update(ws, poses, patches, d(6, 6, 6), d(18), 8, 1, 4),
+        "last_status": lambda m: m.last_status(ws, 8, 1, 4),
+        "check_status": lambda m: m.check_status(f(1)),
+        "gba_setup": lambda m: m.gba_setup(ii, jj, kk, 6, 1, 1, 4, 0, 6),
+        "gba_build": lambda m: m.gba_build(ws, poses, patches, intr, tgt, wgt, lm, ii, jj, 1, 4),
+        "gba_packed": lambda m: m.gba_packed(ws, 8, 1, 4, 1),
+        "gba_solve_update": lambda m: m.gba_solve_update(ws, poses, patches, 8, 1, 4),
+        "gba_info": lambda m: m.gba_info(ws, 8, 1, 4),
+        "workspace_marks": lambda m: m.workspace_marks(ws, 8, 1, 4),
+        "last_dx": lambda m: m.last_dx(ws, 8, 1, 4),
+        "spd_solve": lambda m: m.spd_solve(f(2, 3, 3), f(2, 3, 1)),
+        "spd_solve_factored": lambda m: m.spd_solve_factored(f(2, 3, 3), f(2, 3, 1)),
+        "pg_append": lambda m: m.pg_append(ix, l(4), l(4), *live, counts),
+        "pg_append_dev": lambda m: m.pg_append_dev(ix, l(4), l(4), i(1), *live, counts),
+        "pg_remove": lambda m: m.pg_remove(torch.zeros(16, dtype=torch.bool), ix, 0, 0, False, act,
+                                           back, inac, counts, pos),
+        "pg_remove_window_dev": lambda m: m.pg_remove_window_dev(ix, i(1), 0, 0, False, False, act,
+                                                                 back, inac, counts, pos),
+        "pg_remove_frame_dev": lambda m: m.pg_remove_frame_dev(kf, act, back, counts, pos),
+        "kf_motion": lambda m: m.kf_motion(*live[:3], counts, poses, patches, intr, st, 4, 12.5, kf,
+                                           mag),
+        "kf_shift": lambda m: m.kf_shift(kf, 1, st, *live[:3], counts, [poses, intr], [0, 0], poses,
+                                         l(4), f(8, 7), l(8), i(1)),
+        "edges_loop": lambda m: m.edges_loop(poses, patches, intr, ix, 1, st, 4, i(1), 20, 1000, 15,
+                                             4, 64.0, 4, 1, f(m.edges_loop_work_floats()), l(4),
+                                             l(4), i(1), i(1)),
+        "ba_layer_forward": lambda m: m.ba_layer_forward(poses, patches, intr, tgt, wgt, f(1), 1e-4,
+                                                         ii, jj, kk, 4, 1, False,
+                                                         [0.0, 0.0, 8.0, 8.0], 0.1, True),
+        "ba_layer_backward": lambda m: m.ba_layer_backward(ws, *edge, f(3, 6), f(6), 4, 1, False),
+        "transform_forward": lambda m: m.transform_forward(*edge, False),
+        "transform_backward": lambda m: m.transform_backward(*edge, coords, True, True),
+        "flow_loss_forward": lambda m: m.flow_loss_forward(coords, coords, f(8)),
+        "flow_loss_backward": lambda m: m.flow_loss_backward(coords, coords, f(8), i(1), i(8), f(1)),
+        "pose_loss_forward": lambda m: m.pose_loss_forward(poses, poses),
+        "pose_loss_backward": lambda m: m.pose_loss_backward(poses, poses, f(2)),
+        "frame_flow_distance": lambda m: m.frame_flow_distance(poses, disps, intr),
+        "frame_graph": lambda m: m.frame_graph(f(4, 4)),
+        "rgbd_augment": lambda m: m.rgbd_augment(images, disps, intr, 4, 4, False, [0, 1, 2, 3],
+                                                 1.0, 1.0, 1.0, 0.0, False, False, 1.0, False),
+        "normalize_depth": lambda m: m.normalize_depth(disps, poses),
+        "frame_init": lambda m: m.frame_init(poses, f(8, 3, 3, 3), intr, l(4), d(10), f(2, 3, 3, 3),
+                                             f(4), 2, 0, i(1), 0, i(1), 0, 0.5, 4.0, False),
+        "trajectory": lambda m: m.trajectory(poses, l(4), 4, i(1), f(8, 7), l(8, 2), i(1), 5, False),
+        "frame_prepare": lambda m: m.frame_prepare(u8(8, 8, 3), [4.0, 4.0, 4.0, 4.0], 1.0, False,
+                                                   u8(3, 8, 8)),
+        "trajectory_ate": lambda m: m.trajectory_ate(d(5, 3), d(5), d(6, 3), d(6)),
+        "frame_sample": lambda m: m.frame_sample(f(8, 4, 4), f(16, 4, 4), f(3, 16, 16), f(2, 2),
+                                                 f(3, 2, 8, 3, 3), f(3, 2, 16), f(2, 3, 3, 3),
+                                                 u8(4, 2, 3), 4, 0, i(1)),
+        "probe_median": lambda m: m.probe_median(f(6, 2)),
+        "update_targets": lambda m: m.update_targets(f(1, 8, 2, 3, 3), f(8, 2), f(8, 2), tgt, wgt,
+                                                     8, i(1)),
+        "map_points": lambda m: m.map_points(poses, patches, intr, ix, f(6, 3), 6, i(1)),
+        "match_descriptors": lambda m: m.match_descriptors(f(5, 8), f(6, 8), 0.8, 1.0, 5, i(1), 6,
+                                                           i(1)),
+        "triangulate_tracks": lambda m: m.triangulate_tracks(f(3, 7), f(3, 4), f(6), kps, kps, kps,
+                                                             l(5), l(5), 10.0, 1.0, 2, 1e-3),
+    }
+    # Update: corr_dim 4, 8 edges; its 50 parameter tensors by element count
+    K0 = 4
+    up = [f(384 * K0 if k == 38 else 2 * 384 if k >= 46 else 384 * 384)
+          if (k % 2 == 0 and k not in (8, 22, 30, 42)) else f(2 if k in (47, 49) else 384)
+          for k in range(50)]
+    net, corr = f(8, 384), f(8, K0)
+    dpvo_update = {
+        "plan": lambda m: m.plan(l(8), l(8), ws),
+        "forward": lambda m: m.forward(ws, m.F32, net, net, corr, ii, jj, ws, net, tgt, wgt),
+        "pack_weights_device": lambda m: m.pack_weights_device(up, K0, m.F32, ws),
+        "forward_train": lambda m: m.forward_train(ws, net, net, corr, ii, jj, ws, ws, net, tgt,
+                                                   wgt),
+        "relu_masks": lambda m: m.relu_masks(ws, 8, K0),
+        "backward": lambda m: m.backward(up, ws, ii, jj, K0, net, tgt, wgt, net, net, corr, up, ws),
+    }
+    # BasicEncoder4: output dim 64, one 8 x 8 image
+    shape = [(32, 3, 7)] + [(32, 32, 3)] * 4 + [(64, 32, 3), (64, 64, 3), (64, 32, 1), (64, 64, 3),
+                                                (64, 64, 3), (64, 64, 1)]
+    ep = [f(s[0]) if k % 2 else f(s[0], s[1], s[2], s[2]) for s in shape for k in (0, 1)]
+    img, out = f(1, 3, 8, 8), f(1, 64, 2, 2)
+    dpvo_encoder = {
+        "forward": lambda m: m.forward(ws, m.F32, m.NORM_NONE, img, out, ws),
+        "pack_weights_device": lambda m: m.pack_weights_device(ep, 64, m.NORM_NONE, m.F32, ws),
+        "forward_train": lambda m: m.forward_train(ws, m.F32, m.NORM_NONE, img, out, ws),
+        "backward": lambda m: m.backward(m.NORM_NONE, ep, img, ws, out, ep, ws),
+    }
+    return {"cuda_ba": cuda_ba, "dpvo_update": dpvo_update, "dpvo_encoder": dpvo_encoder}
+
+
+# CPU tensors by contract: the host packers, and solve_system (the loop-closure
+# worker hands it CPU tensors, which it moves to the device itself)
+_CPU_BY_CONTRACT = {"pack_weights", "solve_system"}
+
+
+@pytest.mark.parametrize("module", ["cuda_ba", "dpvo_update", "dpvo_encoder"])
+def test_cpu_tensors_are_rejected_by_every_entry(module):
+    """Every entry that takes a device tensor refuses CPU tensors with its own
+    message, before it builds a device guard from one of them (which dies
+    with torch's INTERNAL ASSERT instead) and before any launch."""
+    import dpvo_amd
+
+    m = dpvo_amd.load_extension(module)
+    calls = _cpu_calls()[module]
+    takes_tensors = {n for n in dir(m) if callable(getattr(m, n)) and not n.startswith("_")
+                     and "Tensor" in getattr(m, n).__doc__.split("\n")[0].rsplit("->", 1)[0]}
+    assert set(calls) == takes_tensors - _CPU_BY_CONTRACT
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match="GPU") as exc:
+            call(m)
+        assert "INTERNAL ASSERT" not in str(exc.value), name
