@@ -679,7 +679,7 @@ int check(const Shape& s, int structure_only, int dtype, size_t ws_bytes, int wi
   if (s.p < 1 || s.p % 2 == 0) return DPVO_ERR_INVALID;
   if (dtype != DPVO_F32 && dtype != DPVO_F64) return DPVO_ERR_INVALID;
   (void)structure_only;
-  if (6 * (int64_t)s.nf > 8192) return DPVO_ERR_UNSUPPORTED;  // dpvo_spd_solve's limit
+  if (6 * (int64_t)s.nf > DPVO_SPD_MAX_N_F64) return DPVO_ERR_UNSUPPORTED;  // dpvo_spd_solve's limit
   if ((int64_t)s.E * kRec > (int64_t)1 << 40) return DPVO_ERR_UNSUPPORTED;
   if (ws_bytes < dpvo_ba_layer_workspace_bytes(s.E, s.M, s.nf, with_backward))
     return DPVO_ERR_WORKSPACE;

@@ -5,8 +5,10 @@
 // One 256-thread workgroup per batch item.  The matrix and the right-hand
 // sides live in LDS when n (n + k) elements fit 160 KB - 64 B (one rhs: fp64
 // n <= 142, fp32 n <= 201; every DPVO training / python_ba system), else in
-// the caller's factor buffer in HBM (same code, global addresses); the work
-// is latency-bound either way (n column steps).
+// the caller's factor buffer in HBM (same code, global addresses; there only
+// the column scratch is in LDS, within the default 64 KB less 64 B for the
+// static fail flag: fp64 n <= 8184, fp32 n <= 16368, beyond that
+// DPVO_ERR_UNSUPPORTED); the work is latency-bound either way (n column steps).
 //   factor: right-looking Cholesky on the lower triangle (torch reads only
 //           the lower triangle of H, cholesky_ex default upper=False):
 //           column j: pivot d = a_jj (d <= 0 or NaN: info = j + 1, the
@@ -27,6 +29,9 @@ namespace {
 
 constexpr int kSpdThreads = 256;
 constexpr size_t kSpdLds = 160 * 1024;
+constexpr size_t kSpdLdsDefault = 64 * 1024;  // what a launch gets without the attribute
+static_assert(DPVO_SPD_MAX_N_F64 == (kSpdLdsDefault - 64) / sizeof(double),
+              "dpvo_hot.h quotes the fp64 limit of the HBM path");
 
 template <typename T>
 __device__ __forceinline__ T spd_sqrt(T v);
@@ -57,8 +62,11 @@ __device__ void spd_factor(T* M, T* lv, int n, int* fail_col, bool mirror) {
       lv[i] = l;
       if (mirror) M[(size_t)j * n + i] = l;  // L^T in the upper triangle (row j)
     }
-    if (tid == 0) M[(size_t)j * n + j] = s;
     __syncthreads();
+    // l_jj only now: before the barrier another wave may still be reading
+    // M[j][j] as the pivot d; the trailing update does not touch the diagonal
+    // of column j, and the next barrier publishes it
+    if (tid == 0) M[(size_t)j * n + j] = s;
     for (int i = j + 1 + tr; i < n; i += kSpdThreads / 32) {
       const T li = lv[i];
       T* row = M + (size_t)i * n;
@@ -174,8 +182,10 @@ int spd_launch(const void* H, const void* B, void* L, void* X, int32_t* info, in
   const int in_lds = full <= kSpdLds - 64;
   const size_t lds = in_lds ? full : sizeof(T) * (size_t)n;
   if (!in_lds && factor && !L) return DPVO_ERR_INVALID;  // the HBM working copy is the factor buffer
-  if (!in_lds && lds > 64 * 1024) return DPVO_ERR_UNSUPPORTED;  // lv alone past 64 KB: n > 8192
-  if (in_lds && lds > 64 * 1024) {
+  // lv alone past the default 64 KB less the margin for the static fail flag
+  // (fp64 n > DPVO_SPD_MAX_N_F64 = 8184, fp32 n > 16368): nothing is launched
+  if (!in_lds && lds > kSpdLdsDefault - 64) return DPVO_ERR_UNSUPPORTED;
+  if (in_lds && lds > kSpdLdsDefault) {
     // the dynamic LDS beyond the default 64 KB (the static fail flag sits on
     // top), set once per device and instantiation
     static bool attr_set[kMaxDevices] = {};

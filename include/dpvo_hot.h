@@ -538,7 +538,11 @@ int dpvo_pg_remove_frame_dev(const int32_t* kf, int64_t* ii, int64_t* jj, int64_
    X = H^-1 B, info[b] = first column whose pivot is not positive (1-based,
    0 = success; LAPACK potrf / cholesky_ex semantics), X = 0 for a failed item.
    factor = 0: H holds a lower factor from a factor = 1 call; X = (H H^T)^-1 B,
-   L and info must be null.  One 256-thread workgroup per item. */
+   L and info must be null.  One 256-thread workgroup per item.
+   Beyond LDS the column scratch alone must fit the default 64 KB less 64 B:
+   n <= DPVO_SPD_MAX_N_F64 in fp64 and twice that in fp32; a larger n is
+   DPVO_ERR_UNSUPPORTED and launches nothing. */
+#define DPVO_SPD_MAX_N_F64 8184
 int dpvo_spd_solve(const void* H, const void* B, void* L, void* X, int32_t* info, int batch, int n,
                    int k, int factor, int dtype, void* stream);
 
@@ -563,7 +567,7 @@ int dpvo_spd_solve(const void* H, const void* B, void* L, void* X, int32_t* info
    g_poses [N, 6] (left tangent), g_patches [M, 3] (x, y, d of the centre).
    E <= 0: DPVO_OK, no launch.  n < fixedp, n > N, p even or < 1, a dtype other
    than F32 / F64, null pointers: DPVO_ERR_INVALID; 6 n_free beyond
-   dpvo_spd_solve's 8192: DPVO_ERR_UNSUPPORTED; short workspace:
+   DPVO_SPD_MAX_N_F64 (8184: 1364 free poses): DPVO_ERR_UNSUPPORTED; short workspace:
    DPVO_ERR_WORKSPACE (in that order).  8 launches forward, 7 backward. */
 size_t dpvo_ba_layer_workspace_bytes(int E, int M, int n_free, int with_backward);
 int dpvo_ba_layer_forward(const void* poses, const void* patches, const void* intrinsics,

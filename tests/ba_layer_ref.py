@@ -276,6 +276,8 @@ def case(name):
         return _random(name, 24, 50, 600, 3, 5)  # 6 * 23 = 138 <= 142: the largest in-LDS fp64 solve
     if name == "h":
         return _random(name, 5, 13, 65, 3, 3).replace(name, ep=-1e6)
+    if name.startswith("w_"):
+        return window_case(name, int(name[2:]))
     raise KeyError(name)
 
 
@@ -297,6 +299,37 @@ def fixture_case(fx):
                 t("weight"), torch.from_numpy(z["ii"]).long(), torch.from_numpy(z["jj"]).long(),
                 torch.from_numpy(z["kk"]).long(), fixedp=int(z["t0"]), ep=1.0,
                 bounds=(-64.0, -64.0, 2 * cx + 64.0, 2 * cy + 64.0))
+
+
+def window_case(name, n_free, fixedp=4):
+    """synthetic.make_dpvo_window (DPVO's own edge pattern, M = 6 patches a
+    frame, lifetime 8: a few thousand edges) with n_free free poses behind
+    `fixedp` fixed ones.  6 n_free = 96: the pose system factors in LDS above
+    64 KB; 144: in the workspace in HBM, where the backward's solve reads the
+    factor.  The seed is advanced until the margins hold (deterministic)."""
+    from dpvo_amd.synthetic import make_dpvo_window
+
+    for seed in range(50):
+        G = make_dpvo_window(n=n_free + fixedp, M=6, lifetime=8, seed=seed)
+        c = Case(name, unit(G.poses.double()), G.patches.double(), G.intrinsics.double(),
+                 G.target.double(), G.weight.double(), G.ii, G.jj, G.kk, fixedp=fixedp, ep=100.0)
+        assert c.n == n_free + fixedp
+        if all(margins(c)):
+            return c
+    raise AssertionError(f"no seed gives case {name} its margins")
+
+
+WINDOW_CASES = ["w_16", "w_24"]  # 6 n_free = 96 (LDS above 64 KB), 144 (HBM)
+
+
+def permuted(c, seed=11):
+    """The case with its edges under one fixed permutation -> (case, perm):
+    the same sums in another order."""
+    perm = torch.randperm(c.ii.numel(), generator=torch.Generator().manual_seed(seed))
+    cp = c.replace(c.name + "_perm", ii=c.ii[perm], jj=c.jj[perm], kk=c.kk[perm],
+                   targets=c.targets[perm], weights=c.weights[perm])
+    cp.n = c.n
+    return cp, perm
 
 
 GATE_BOUNDS = (25.0, 20.0, 135.0, 100.0)

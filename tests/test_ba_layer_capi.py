@@ -45,17 +45,17 @@ def test_rejections_and_precedence(lib, call):
     assert call(lib, dtype=7) == 1
     assert call(lib, n=9) == 1
     assert call(lib, ptr=None) == 1
-    # UNSUPPORTED: 6 n_free beyond dpvo_spd_solve's 8192 (1366 free poses)
-    assert call(lib, N=2000, n=1367, fixedp=1) == 3
-    assert call(lib, N=2000, n=1366, fixedp=1, ws=small) == 4   # 6 * 1365 = 8190 is accepted
-    assert call(lib, N=2000, n=1367, fixedp=1, so=1, ws=small) == 4  # structure only: no pose system
+    # UNSUPPORTED: 6 n_free beyond dpvo_spd_solve's limit, 8184 (1365 free poses)
+    assert call(lib, N=2000, n=1366, fixedp=1) == 3
+    assert call(lib, N=2000, n=1365, fixedp=1, ws=small) == 4   # 6 * 1364 = 8184 is accepted
+    assert call(lib, N=2000, n=1366, fixedp=1, so=1, ws=small) == 4  # structure only: no pose system
     # WORKSPACE
     assert call(lib, ws=small) == 4
     # precedence: INVALID wins over UNSUPPORTED and WORKSPACE, UNSUPPORTED over WORKSPACE
-    assert call(lib, N=2000, n=1367, p=2, ws=small) == 1
-    assert call(lib, N=2000, n=1367, dtype=F16, ws=small) == 1
+    assert call(lib, N=2000, n=1366, p=2, ws=small) == 1
+    assert call(lib, N=2000, n=1366, dtype=F16, ws=small) == 1
     assert call(lib, n=1, fixedp=2, ws=small) == 1
-    assert call(lib, N=2000, n=1367, ws=small) == 3
+    assert call(lib, N=2000, n=1366, ws=small) == 3
 
 
 def test_workspace_bytes(lib):
